@@ -22,7 +22,13 @@ max-over-ranks), never on the GPU.  --torch runs the same step through the
 torch harness instead (torch tensors and streams, torch.distributed's
 all-reduce).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+A plain run sets up, settles and warms up, times the K steps and prints the
+result line.  --full adds what the headline figure does not need: the CPU
+baseline, the live stream floor per launch shape and the committed PMC
+traffic (null in a plain run's line).  --dump-outputs DIR writes what the last
+timed step computed (the hit counters and a fixed sample of the verdicts) as
+DIR/<name>.npy; the inputs are the same on every run with the same arguments.
 N>1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) the
 ranks run directly; otherwise bench.py starts torch.distributed.run itself as
 a child process, before anything touches the GPU, and exits with its status.
@@ -58,12 +64,25 @@ def parse():
                          "over the first ~10 ms of work, whatever --warmup is")
     ap.add_argument("--config", type=int, default=3, choices=[2, 3, 4, 5])
     ap.add_argument("--packets", type=int, default=0, help="packets per GPU (default: config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything beside the headline figure: the CPU baseline "
+                         "(--cpu-sample), the live stream floor per launch shape and the committed PMC traffic "
+                         "of the roofline; a plain run skips them and reports null there")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: "
+                         "counters.npy (the merged per-rule hit counters, float64), verdicts.npy (a fixed seeded "
+                         "sample of the verdicts, float32; rank r > 0 writes verdicts_r<r>.npy) and "
+                         "verdict_index.npy (the sampled packets' batch indices, float64)")
+    ap.add_argument("--dump-sample", type=int, default=1 << 22,
+                    help="--dump-outputs: verdicts written over all ranks (the default: 16 MiB as float32 and "
+                         "32 MiB of indices)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 21,
-                    help="packets timed on the host for the CPU baseline (0: skip)")
+                    help="--full: packets timed on the host for the CPU baseline (0: skip)")
     ap.add_argument("--faithful-sample", type=int, default=4096)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (default: every core this process may use)")
-    ap.add_argument("--no-stream-floor", action="store_true", help="skip the live stream-floor measurement")
+    ap.add_argument("--no-stream-floor", action="store_true",
+                    help="--full: skip the live stream-floor measurement")
     ap.add_argument("--opt", action="append", default=[],
                     help="engine option key=value (cls_engine_set_option; A/B measurements)")
     ap.add_argument("--torch", action="store_true",
@@ -157,6 +176,22 @@ def cpu_baseline(acl, spec, sample: int, faithful_sample: int, threads: int = 0)
                                      "per rule per packet, aclengine_mock.go:500,514), %.1f s"
                                      % (faithful_sample, dt2)}
     return out
+
+
+def dump_outputs(d: str, rank: int, world: int, sample: int, verdict: np.ndarray, counters) -> None:
+    """--dump-outputs: what a caller of the timed path holds after the last
+    timed step.  The merged hit counters cover every packet of every rank
+    (rank 0 writes them); of each rank's verdicts a fixed sample is written,
+    the same packets on every run (seeded by the rank alone), and all of them
+    when the batch is no larger than the sample."""
+    os.makedirs(d, exist_ok=True)
+    n, k = len(verdict), max(1, sample // world)
+    idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(0xC0175EED + rank).integers(0, n, k))
+    sfx = "_r%d" % rank if rank else ""
+    np.save(os.path.join(d, "verdicts%s.npy" % sfx), verdict[idx].astype(np.float32))
+    np.save(os.path.join(d, "verdict_index%s.npy" % sfx), idx.astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(d, "counters.npy"), np.asarray(counters).astype(np.float64))
 
 
 def pmc_traffic(cfg: int, n: int):
@@ -330,7 +365,11 @@ def main():
     lds = info["lds_bytes"] if af == 4 else info["lds_bytes_v16"]
     resident = info["lds_resident"] if af == 4 else info["lds_resident_v16"]
     two_per_cu = not resident or 2 * (lds + 16) <= 160 * 1024     # the classify launch's workgroups per CU
-    if not args.no_stream_floor:
+    if args.dump_outputs:
+        # the last timed step's counter buffer, merged over the ranks where a group exists
+        dump_outputs(args.dump_outputs, rank, world, args.dump_sample, verdict.cpu().numpy(),
+                     counters[(i - 1) % nbuf].cpu().numpy())
+    if args.full and not args.no_stream_floor:
         # one launch covers at most 2^30 packets (the kernels' 32-bit offsets):
         # time the floor on that prefix and scale to the batch
         m = min(n, 1 << 30)
@@ -349,9 +388,9 @@ def main():
         mpps = total / wall / 1e6
         alg_bytes = n * BYTES_PER_PKT[af] + (R + 1) * 8
         achieved = alg_bytes / (avg_k / 1e3) / 1e9
-        traffic, traffic_src = pmc_traffic(args.config, n)
+        traffic, traffic_src = pmc_traffic(args.config, n) if args.full else (None, "not read (--full)")
         cpu = None
-        if world == 1 and args.cpu_sample:
+        if args.full and world == 1 and args.cpu_sample:
             cpu = cpu_baseline(acl, spec, args.cpu_sample, args.faithful_sample, args.cpu_threads)
         if af == 4:
             wl = "config%d: %d-rule global ACL (%d pods), %d IPv4 TCP/UDP packets per GPU" % (
@@ -368,6 +407,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(wall / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -525,6 +565,8 @@ def main_native(args, rank, world, local):
         np.save(os.path.join(args.dump, "verdict_r%d.npy" % rank), b.download(_abi.BF_VERDICT))
         if rank == 0:
             np.save(os.path.join(args.dump, "counters.npy"), counters)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, args.dump_sample, b.download(_abi.BF_VERDICT), counters)
     avg_k = float(np.mean(kms)) if kms else float("nan")
     med_k = float(np.median(kms)) if kms else float("nan")
     periods = list(np.diff(starts) / every) if len(starts) > 1 else []      # timed steps `every` apart
@@ -535,7 +577,7 @@ def main_native(args, rank, world, local):
     resident = info["lds_resident"] if af == 4 else info["lds_resident_v16"]
     two_per_cu = not resident or 2 * (lds + 16) <= 160 * 1024
     floor_ms = shape_ms = None
-    if not args.no_stream_floor:
+    if args.full and not args.no_stream_floor:
         m = min(n, 1 << 30)
         m -= m % (256 if af == 16 else 4)
         p = lambda f: b.field_ptr(0, f)  # noqa: E731
@@ -561,9 +603,9 @@ def main_native(args, rank, world, local):
         mpps = total / wall / 1e6
         alg_bytes = n * BYTES_PER_PKT[af] + (R + 1) * 8
         achieved = alg_bytes / (avg_k / 1e3) / 1e9
-        traffic, traffic_src = pmc_traffic(args.config, n)
+        traffic, traffic_src = pmc_traffic(args.config, n) if args.full else (None, "not read (--full)")
         cpu = None
-        if world == 1 and args.cpu_sample:
+        if args.full and world == 1 and args.cpu_sample:
             cpu = cpu_baseline(acl, spec, args.cpu_sample, args.faithful_sample, args.cpu_threads)
         if af == 4:
             wl = "config%d: %d-rule global ACL (%d pods), %d IPv4 TCP/UDP packets per GPU" % (
@@ -581,6 +623,7 @@ def main_native(args, rank, world, local):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(wall / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",

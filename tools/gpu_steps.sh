@@ -4,7 +4,7 @@
 #
 # usage: tools/gpu_steps.sh <tag> <step> [<step> ...]
 #   parity[:files]     pytest -m gpu (all tests, or the comma-separated files)
-#   bench:<config>     one driver-flag bench line (--steps 20 --warmup 5)
+#   bench:<config>     one bench line with the stream floor (--steps 20 --warmup 5 --full)
 #   events:<config>    bench lines with --events 2 / 1 / 0 (what events cost)
 #   kstats:<config>    rocprofv3 --kernel-trace --stats of a bench run, and the
 #                      gaps between the last launches (tools/gaps.py)
@@ -42,7 +42,7 @@ for step in "$@"; do
     timeout -k 10 900 python -u -m pytest $files -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -40 $O/pytest.log; exit 1; }
     tail -2 $O/pytest.log ;;
   bench)
-    timeout -k 10 300 python bench.py --config $arg $B > $O/bench_c$arg.json 2> $O/bench_c$arg.err
+    timeout -k 10 300 python bench.py --config $arg $B --full > $O/bench_c$arg.json 2> $O/bench_c$arg.err
     python3 tools/jl.py $O/bench_c$arg.json value ms_per_step step_ms_median roofline.kernel_ms_median roofline.stream_floor_ms roofline.frac ;;
   benchk)
     # benchk:<config>[:<tag>[:key=value...]]: the bench line under rocprofv3 kernel stats (no stream floor)
