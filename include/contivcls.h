@@ -246,8 +246,10 @@ int cls_classify(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pkts,
  * evaluation terminated, R for the default DENY (:667) -- the counter
  * cls_classify adds the packet to.  No counters are touched.  Flags:
  * CLS_F_DEVICE (device arrays, rule_out 4-byte aligned; stream-ordered),
- * else host arrays and the call returns with the results.  Replaces, for a
- * batch, the rule index evalACL computes and logs per call. */
+ * else host arrays and the call returns with the results.  A table that has
+ * no 16-byte classifier (cls_table_info's has_v16 == 0) returns CLS_E_INVAL
+ * for a CLS_AF_V16 batch, as cls_classify does.  Replaces, for a batch, the
+ * rule index evalACL computes and logs per call. */
 int cls_classify_rules(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pkts,
                        uint64_t n, uint8_t* verdict_out, uint32_t* rule_out,
                        uint32_t flags, void* stream);

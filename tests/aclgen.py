@@ -178,6 +178,61 @@ def random_traffic(seed: int, n: int, pool: PrefixPool, other_proto: bool = True
     return dict(src=src, dst=dst, dport=dport, proto=proto, sport=sport)
 
 
+def _v4_net(cidr: str):
+    """(first, last) of a plain dotted-quad a.b.c.d/n network, None for an
+    empty, malformed or non-IPv4 string (host bits masked, as ParseCIDR)."""
+    try:
+        addr, ln = cidr.split("/")
+        q = [int(x) for x in addr.split(".")]
+        ln = int(ln)
+    except ValueError:
+        return None
+    if len(q) != 4 or not all(0 <= x <= 255 for x in q) or not 0 <= ln <= 32 or ":" in cidr:
+        return None
+    size = 1 << (32 - ln)
+    first = ((q[0] << 24) | (q[1] << 16) | (q[2] << 8) | q[3]) & ~(size - 1) & 0xFFFFFFFF
+    return first, first + size - 1
+
+
+def directed_traffic(rules, base, seed: int, share: float = 0.75):
+    """A copy of the IPv4 batch ``base`` (random_traffic) with about ``share``
+    of its packets aimed at a randomly chosen rule each: src and dst at the
+    first, the last or a random address of the rule's networks (a field is
+    left alone when its network is empty, malformed or not IPv4), proto one of
+    the rule's L4 kinds, dport the lower bound, the upper bound or a random
+    port of that kind's destination range.  The other packets (the protocols
+    > 2 among them) stay as they are, so a batch still reaches the default
+    DENY and the OTHER image.  Deterministic in ``seed``."""
+    rng = random.Random(seed)
+    tr = {k: v.copy() for k, v in base.items()}
+    n = len(tr["dport"])
+
+    def pick(lo, hi):
+        return [lo, hi, rng.randint(lo, hi)][rng.randrange(3)]
+
+    for i in range(n):
+        if not rules or rng.random() >= share:
+            continue
+        r = rules[rng.randrange(len(rules))]
+        ipr = r.matches.ip_rule if r.matches is not None else None
+        if ipr is None:
+            continue
+        if ipr.ip is not None:
+            for key, cidr in (("src", ipr.ip.source_network), ("dst", ipr.ip.destination_network)):
+                net = _v4_net(cidr) if cidr else None
+                if net is not None:
+                    tr[key][i] = pick(*net)
+        kinds = [(p, l4) for p, l4 in ((0, ipr.tcp), (1, ipr.udp), (2, ipr.icmp)) if l4 is not None]
+        if not kinds:
+            continue
+        p, l4 = kinds[rng.randrange(len(kinds))]
+        tr["proto"][i] = p
+        pr = l4.destination_port_range if p < 2 else None
+        if pr is not None and 0 <= pr.lower_port <= pr.upper_port <= 65535:
+            tr["dport"][i] = pick(pr.lower_port, pr.upper_port)
+    return tr
+
+
 def single_port_acl(seed: int, n_rules: int = 120, n_prefixes: int = 8):
     """Rules in renderACL's shape (acl_renderer.go:342-374): dst port a single
     port or any (ContivRule.DestPort, 0 = any), no source port.  Port classes

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
-from aclgen import random_acl, random_traffic
+from aclgen import directed_traffic, random_acl, random_traffic
 from scenario_replay import load_scenarios, replay
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +140,10 @@ def test_all_kernel_variants(eng, seed, kind, libopt):
     h = Image(compile_blob(_abi.CRules(rules))).h
     assert (h.mode, h.list_mode) == VARIANTS[kind], kind
     tr = random_traffic(seed + 11, 30000, pool)
+    _assert_same(_gpu(eng, rules, tr), _oracle(rules, tr))
+    # a second batch aimed at the rules: the random one mostly ends at the
+    # default DENY on the bit-vector and scan tables (test_directed_traffic_cpu.py)
+    tr = directed_traffic(rules, random_traffic(seed + 11, 4099, pool), seed)
     _assert_same(_gpu(eng, rules, tr), _oracle(rules, tr))
 
 

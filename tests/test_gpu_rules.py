@@ -23,20 +23,64 @@ def eng():
     e.close()
 
 
-def _check(eng, rules, tr, af=4, **opts):
-    cr = oracle.rules_to_c(rules)
-    ov, oh = oracle.classify_hits(cr, tr["src"], tr["dst"], tr["dport"], tr["proto"], af=af)
-    t = eng.put_table("r", rules)
+def to_device(tr):
+    """The batch as torch device tensors (fresh allocations: 16-byte aligned)."""
+    import torch
+    signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint16): np.int16}
+    return {k: torch.from_numpy(np.ascontiguousarray(v).view(signed.get(v.dtype, v.dtype))).cuda()
+            for k, v in tr.items() if k in ("src", "dst", "dport", "proto")}
+
+
+PAD = 64            # elements after a device output that the call must leave alone
+
+
+def _rules_on_device(eng, t, dev, verdict):
+    """cls_classify_rules over device tensors.  The outputs have PAD more
+    elements than the batch, all ones, which must still be there afterwards;
+    the batch's own words start as 3 (no ACLAction, slot 0), so that a packet
+    the slot kernel skipped shows as a wrong verdict."""
+    import torch
+    n = len(dev["dport"])
+    rb = torch.full((n + PAD,), -1, dtype=torch.int32, device="cuda")
+    rb[:n] = 3
+    vb = torch.full((n + PAD,), 0xFF, dtype=torch.uint8, device="cuda") if verdict else None
+    eng.classify_rules(t, dev["src"], dev["dst"], dev["dport"], dev["proto"], verdict=vb, rules=rb)
+    torch.cuda.synchronize()
+    r = rb.cpu().numpy().view(np.uint32)
+    assert (r[n:] == 0xFFFFFFFF).all(), "rule_out written past the batch: %s" % r[n:]
+    v = None
+    if verdict:
+        v = vb.cpu().numpy()
+        assert (v[n:] == 0xFF).all(), "verdict_out written past the batch: %s" % v[n:]
+        v = v[:n]
+    return v, r[:n]
+
+
+def _check(eng, rules, tr, af=4, table=None, want=None, dev=None, verdict=True):
+    """(verdict, rule) of cls_classify_rules against the oracle's, element by
+    element, and the rules' histogram against cls_classify's counters on the
+    same table and batch.  tr: the batch in host arrays; dev: the same batch
+    as torch device tensors, then the call takes those (verdict=False:
+    without a verdict array).  table / want: a table already put and the
+    oracle's (verdict, rule) of tr, for callers that share them."""
+    if want is None:
+        want = oracle.classify_hits(oracle.rules_to_c(rules), tr["src"], tr["dst"], tr["dport"], tr["proto"], af=af)
+    ov, oh = want
+    t = table if table is not None else eng.put_table("r", rules)
     try:
-        v, r = eng.classify_rules(t, tr["src"], tr["dst"], tr["dport"], tr["proto"])
-        bad = np.nonzero((v != ov) | (r != oh))[0]
+        if dev is None:
+            v, r = eng.classify_rules(t, tr["src"], tr["dst"], tr["dport"], tr["proto"])
+        else:
+            v, r = _rules_on_device(eng, t, dev, verdict)
+        bad = np.nonzero(r != oh if v is None else (v != ov) | (r != oh))[0]
         assert len(bad) == 0, "mismatch at %s: got %s / %s want %s / %s" % (
-            bad[:6], v[bad[:6]], r[bad[:6]], ov[bad[:6]], oh[bad[:6]])
+            bad[:6], None if v is None else v[bad[:6]], r[bad[:6]], ov[bad[:6]], oh[bad[:6]])
         _, c = eng.classify(t, tr["src"], tr["dst"], tr["dport"], tr["proto"])
         np.testing.assert_array_equal(np.bincount(r, minlength=len(rules) + 1).astype(np.uint64), c)
         return t.info()
     finally:
-        eng.del_table(t)
+        if table is None:
+            eng.del_table(t)
 
 
 @pytest.mark.parametrize("seed", range(4))

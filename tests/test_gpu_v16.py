@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
-from aclgen import mix_families, random_acl16, random_traffic, random_traffic16
+from aclgen import directed_traffic, mix_families, random_acl16, random_traffic, random_traffic16
 from test_gpu_parity import VARIANTS, _assert_same, _gpu, variant_acl
 
 pytestmark = pytest.mark.gpu
@@ -50,8 +50,11 @@ def test_v16_all_kernel_variants(eng, seed, kind, libopt):
     if kind.endswith("_pc"):
         libopt.set("list_mode_max", "2", eng)
     libopt.set("trie", "1" if kind.startswith("trie") else "0", eng)
-    rules, pool = variant_acl(kind, seed)
-    rules, tr = mix_families(rules, random_traffic(seed + 11, 20000, pool), seed)
+    rules4, pool = variant_acl(kind, seed)
+    rules, tr = mix_families(rules4, random_traffic(seed + 11, 20000, pool), seed)
+    _assert_same(_gpu(eng, rules, tr), _oracle16(rules, tr, fast=True))
+    # a second batch aimed at the rules (test_directed_traffic_cpu.py); the same seed gives the same twin table
+    rules, tr = mix_families(rules4, directed_traffic(rules4, random_traffic(seed + 11, 4099, pool), seed), seed)
     _assert_same(_gpu(eng, rules, tr), _oracle16(rules, tr, fast=True))
 
 

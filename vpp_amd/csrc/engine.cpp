@@ -809,6 +809,9 @@ static int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt
     const std::shared_ptr<Table> t = it->second;
     const bool v16 = pk->af == CLS_AF_V16;
     if (!v16 && pk->af != CLS_AF_V4) return fail(e, CLS_E_INVAL, "af must be CLS_AF_V4 or CLS_AF_V16");
+    // table_upload leaves every 16-byte device buffer empty for such a table
+    if (v16 && !t->p16.ok)
+        return fail(e, CLS_E_INVAL, "no 16-byte classifier for this table: %s", t->p16.why.c_str());
     if (n && (!pk->dport || !pk->proto || (v16 ? !pk->src16 || !pk->dst16 : !pk->src4 || !pk->dst4)))
         return fail(e, CLS_E_INVAL, "missing packet arrays");
     if (n && !rule_out) return fail(e, CLS_E_INVAL, "rule_out is NULL");
