@@ -185,7 +185,7 @@ int cls_abi_version(void);
  * The switches force compiler choices (list_mode, list_mode_max, trie, wide,
  * orient=src|dst, lds_budget, src_search, phash_dense, v16_src_search,
  * v16_src_trie) for later cls_table_put / cls_acl_put compiles, and launch
- * plans (other_cap, wg_per_cu, conn_bitmap, conn_pair, conn_pre_rules,
+ * plans (other_cap, wg_per_cu, conn_bitmap, conn_pair, conn_pair16, conn_pre_rules,
  * conn_pre_narrow, pair_qcap, pair_lq, pair_other_global, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * debug_modes, debug_conn, debug_floor) for later calls; every one keeps
@@ -549,7 +549,11 @@ int cls_conn_bitmap_eval(const cls_rule* rules, uint32_t n_rules, const uint32_t
  * ones) and fe_n u32 representatives at fe_val -- and `core` is the IPv4
  * classifier over the rules restated on representatives (magic 0x434C3136
  * "CL16"; its linear rules are in representative space too).  Returns
- * CLS_E_INVAL when the table has no 16-byte classifier.
+ * CLS_E_INVAL when the table has no 16-byte classifier.  Option pair4=1 (as
+ * cls_compile_v4's): the connection pair launch's image instead, in the main
+ * image's orientation -- the same front-end tables and source-search
+ * trailer, a core of four cells per class (the fourth for protocols > 2)
+ * with slots of its own, and no OTHER image (off_other 0).
  */
 typedef struct cls_image_v16_header {
     cls_image_v4_header core;

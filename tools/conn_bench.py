@@ -10,7 +10,14 @@ tensors (CLS_F_DEVICE, ``hbm_resident``: the median wall time of --iters calls),
 and the C oracle (one thread) on a sample.  Prints one JSON line.  --count 1 times CLS_F_COUNT batches (per-(ACL, rule) counters)
 beside the plain ones; --locals sets the number of local ACLs (12: a rule
 pool that fits LDS).
-usage: python tools/conn_bench.py [--n 4194304] [--iters 5] [--locals 64]
+--af 16: the mixed-family layout (CLS_AF_V16) -- the config-5 table (IPv4 and
+IPv6 networks) as the global ACL, random 16-byte local ACLs, endpoints of both
+families (half of the connections from the config-5 stream, the others
+around the locals' prefixes); the same line, 46 algorithmic bytes per
+connection.  The connection stream floor is IPv4 only: the 16-byte line
+reports the 16-byte classify stream's floor (35 B read, 1 B written per
+packet) beside the 37 + 1 B of a pair launch (k16_pair.hip).
+usage: python tools/conn_bench.py [--n 4194304] [--iters 5] [--locals 64] [--af 4|16]
 """
 import argparse
 import json
@@ -23,8 +30,50 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-from aclgen import random_traffic  # noqa: E402
+from aclgen import random_acl16, random_traffic, random_traffic16  # noqa: E402
 from test_gpu_connect_scale import build, oracle_connections  # noqa: E402
+
+
+def build16(eng, seed, n_local, n_if=80):
+    """build() of test_gpu_connect_scale for --af 16: the config-5 table as it
+    is rendered (already both families) as the global ACL, random_acl16 locals."""
+    import random
+
+    from vpp_amd import workload
+    rng = random.Random(seed)
+    glob, spec, _ = workload.config(5)
+    ifs = ["if%d" % i for i in range(n_if)]
+    bind = {name: [None, None] for name in ifs}
+    acls = [("global", glob.rules, ["if0", "if1"], ["if0", "if2"])]
+    pool = None
+    for k in range(n_local):
+        size = rng.choice([1, 3, 12, 40, 150, 300])
+        rules, pool = random_acl16(1000 + k, size, weird=rng.choice([0.0, 0.003, 0.15]))
+        acls.append(("local%d" % k, rules, rng.sample(ifs[3:], rng.randrange(1, 3)),
+                     rng.sample(ifs[3:], rng.randrange(0, 3))))
+    by_name = {}
+    for name, rules, ing, eg in acls:
+        assert eng.acl_put(name, rules, ing, eg) == 0
+        by_name[name] = rules
+        for i in ing:
+            bind[i][0] = name
+        for i in eg:
+            bind[i][1] = name
+    return ifs, bind, by_name, pool, spec
+
+
+def traffic16(n, pool, spec, half, rng):
+    """Mixed-family endpoints: the config-5 stream where `half`, else
+    addresses around the locals' prefixes (a base of 2^17 connections drawn
+    with replacement: the address generator is per-address Python)."""
+    import oracle
+    base = random_traffic16(7, min(n, 1 << 17), pool)
+    pick = rng.integers(0, len(base["proto"]), n)
+    tr = {f: v[pick] for f, v in base.items()}
+    g = oracle.gen_traffic_v16(spec, 0, n)
+    for f in ("src", "dst", "dport", "proto"):
+        tr[f][half] = g[f][half]
+    return tr
 
 
 def main():
@@ -37,20 +86,28 @@ def main():
     ap.add_argument("--other-proto", type=int, default=1, help="6%% of packets with protocol > 2")
     ap.add_argument("--locals", type=int, default=64)
     ap.add_argument("--count", type=int, default=1)
+    ap.add_argument("--af", type=int, default=4, choices=[4, 16], help="16: mixed-family batches (CLS_AF_V16)")
     ap.add_argument("--no-check", action="store_true", help="diagnostic builds: skip the parity asserts")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="library tuning switch (cls_engine_set_option), repeatable")
     a = ap.parse_args()
     from vpp_amd.engine import Engine
     eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
-    ifs, bind, by_name, pool, spec = build(eng, 0, cfg=3, n_local=a.locals)
     n = a.n
-    tr = random_traffic(7, n, pool, other_proto=bool(a.other_proto))
     rng = np.random.default_rng(7)
     half = rng.random(n) < 0.5
-    tr["src"][half] = rng.choice(spec["pod_ips"].astype(np.uint32), half.sum())
-    dsts = spec["dst_addrs"].astype(np.uint32)
-    tr["dst"][half] = rng.choice(dsts, half.sum()) | rng.integers(0, 256, half.sum()).astype(np.uint32)
+    if a.af == 16:
+        ifs, bind, by_name, pool, spec = build16(eng, 0, a.locals)
+        tr = traffic16(n, pool, spec, half, rng)
+        if a.other_proto:                                # (the config-5 stream has none)
+            oth = half & (rng.random(n) < 0.06)
+            tr["proto"][oth] = 47
+    else:
+        ifs, bind, by_name, pool, spec = build(eng, 0, cfg=3, n_local=a.locals)
+        tr = random_traffic(7, n, pool, other_proto=bool(a.other_proto))
+        tr["src"][half] = rng.choice(spec["pod_ips"].astype(np.uint32), half.sum())
+        dsts = spec["dst_addrs"].astype(np.uint32)
+        tr["dst"][half] = rng.choice(dsts, half.sum()) | rng.integers(0, 256, half.sum()).astype(np.uint32)
     ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
     si = np.where(half, rng.integers(0, 2, n), rng.integers(0, len(ifs), n))
     di = rng.integers(0, len(ifs), n)
@@ -95,8 +152,12 @@ def main():
         from vpp_amd import _abi
         from vpp_amd.engine import _ptr
         out = torch.empty(n, dtype=torch.uint8, device="cuda")
-        pk = _abi.PktSoa(_abi.AF_V4, _ptr(dargs[2]), _ptr(dargs[3]), None, None, _ptr(dargs[5]), _ptr(dargs[6]),
-                         _ptr(dargs[4]))
+        if a.af == 16:
+            pk = _abi.PktSoa(_abi.AF_V16, None, None, _ptr(dargs[2]), _ptr(dargs[3]), _ptr(dargs[5]), _ptr(dargs[6]),
+                             _ptr(dargs[4]))
+        else:
+            pk = _abi.PktSoa(_abi.AF_V4, _ptr(dargs[2]), _ptr(dargs[3]), None, None, _ptr(dargs[5]), _ptr(dargs[6]),
+                             _ptr(dargs[4]))
         cs = _abi.ConnSoa(pk, _ptr(dargs[0]), _ptr(dargs[1]))
         fl = _abi.F_DEVICE | (_abi.F_COUNT if count else 0)
         fn, h, csr, op = _abi.lib().cls_connect_batch, eng.h, C.byref(cs), _ptr(out)
@@ -142,14 +203,26 @@ def main():
     # same arrays (cls_stream_floor_conn: the same reads and write, no
     # evaluation)
     # (the product path: device batches through the C ABI, back to back)
-    floor = eng.stream_floor_conn(*dargs, reps=20)
-    roof = {"bound": "hbm", "bytes_per_connection": 22, "peak": 8000.0, "unit": "GB/s",
-            "achieved": round(22 * n / abi_piped / 1e9, 1), "frac": round(22 * n / abi_piped / 8e12, 4),
-            "stream_floor_ms": round(floor, 4), "frac_of_stream_floor": round(floor / (abi_piped * 1e3), 4),
-            "timed": "abi_pipelined_ms_per_batch"}
+    if a.af == 16:
+        # 46 B: 16-B src and dst in place of the 4-B ones.  No connection
+        # stream floor for this layout: the 16-byte classify stream's (35 B
+        # read + 1 B written per packet), which a pair launch of one large ACL
+        # (37 B read + 1 B written per connection) is measured against.
+        floor = eng.stream_floor(dargs[2], dargs[3], dargs[6], dargs[4], vout, reps=20)
+        roof = {"bound": "hbm", "bytes_per_connection": 46, "peak": 8000.0, "unit": "GB/s",
+                "achieved": round(46 * n / abi_piped / 1e9, 1), "frac": round(46 * n / abi_piped / 8e12, 4),
+                "classify16_stream_floor_ms": round(floor, 4), "classify16_stream_bytes": 36,
+                "pair_launch_bytes": 38, "pair_launch_floor_ms": round(floor * 38 / 36, 4),
+                "timed": "abi_pipelined_ms_per_batch"}
+    else:
+        floor = eng.stream_floor_conn(*dargs, reps=20)
+        roof = {"bound": "hbm", "bytes_per_connection": 22, "peak": 8000.0, "unit": "GB/s",
+                "achieved": round(22 * n / abi_piped / 1e9, 1), "frac": round(22 * n / abi_piped / 8e12, 4),
+                "stream_floor_ms": round(floor, 4), "frac_of_stream_floor": round(floor / (abi_piped * 1e3), 4),
+                "timed": "abi_pipelined_ms_per_batch"}
     k = a.cpu_sample
     t1 = time.perf_counter()
-    want, _ = oracle_connections(bind, by_name, ifs, si[:k], di[:k], {f: v[:k] for f, v in tr.items()}, 4)
+    want, _ = oracle_connections(bind, by_name, ifs, si[:k], di[:k], {f: v[:k] for f, v in tr.items()}, a.af)
     cpu_dt = time.perf_counter() - t1
     if not a.no_check:
         assert np.array_equal(out[:k], want), "connection verdicts differ from the oracle"
@@ -166,15 +239,15 @@ def main():
     cores = cpu_share()
     trk = {f: v[:kf] for f, v in tr.items()}
     oracle.connect_fast(tabs, if_in, if_out, si[:1024], di[:1024], {f: v[:1024] for f, v in tr.items()},
-                        nthreads=cores)
+                        af=a.af, nthreads=cores)
     t2 = time.perf_counter()
-    fast = oracle.connect_fast(tabs, if_in, if_out, si[:kf], di[:kf], trk, nthreads=cores)
+    fast = oracle.connect_fast(tabs, if_in, if_out, si[:kf], di[:kf], trk, af=a.af, nthreads=cores)
     fast_dt = time.perf_counter() - t2
     if not a.no_check:
         assert np.array_equal(fast, out[:kf]), "the fast CPU port differs from the GPU verdicts"
     print(json.dumps({
         "metric": "connections classified per second (testConnection, up to 4 ACL evaluations each)",
-        "value": round(n / abi_piped / 1e6, 3), "unit": "Mconn/s", "n": n,
+        "value": round(n / abi_piped / 1e6, 3), "unit": "Mconn/s", "n": n, "af": a.af,
         "ms_per_batch": round(abi_piped * 1e3, 4),
         "timed": "device batches through cls_connect_batch, back to back (HBM-resident, stream-ordered)",
         "host_arrays": {"value": round(n / dt / 1e6, 3), "unit": "Mconn/s", "ms_per_batch": round(dt * 1e3, 3),

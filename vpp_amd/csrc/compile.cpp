@@ -1390,7 +1390,10 @@ static bool build_cls4_one(const std::vector<SemRule>& sem, uint32_t n_rules, Cl
             // the trie walks, in a fraction of its LDS (the trie's first level
             // alone is 1 KiB): take the interval search
             if (tr && tmode != 1 && cand[1] == 0 && 3u + img.trie_depth >= isearch) continue;
-            const bool ok = cell_ok(lm) && place_counters(img, budget, partial);
+            bool ok = cell_ok(lm) && place_counters(img, budget, partial);
+            // (Cls4Opts::lds_image_only: the image alone decides -- the tiers
+            // above are still laid out, for the header)
+            if (opt && opt->lds_image_only) ok = img.lds_ok = cell_ok(lm) && img.img_bytes + kLdsReserved <= budget;
             if (dbg)
                 std::fprintf(stderr, "list mode %u%s%s%s: lds %u img %u ctr %u lctr %u ctr16 %u -> %s\n", img.list_mode,
                              tr ? " trie" : "", wide ? " wide" : "", partial ? " (partial)" : "", img.lds_bytes,
@@ -1576,7 +1579,10 @@ bool cuckoo6(const std::vector<std::array<uint32_t, 4>>& keys, uint32_t cap, uin
 
 }  // namespace
 
-static bool build_cls16_one(const std::vector<SemRule>& sem, uint32_t n_rules, Cls16Image& img, std::string& why) {
+// with_other: the core gets a fourth cell per class for protocols > 2
+// (Cls4Opts::with_other: the connection pair launch's image, build_pair16)
+static bool build_cls16_one(const std::vector<SemRule>& sem, uint32_t n_rules, Cls16Image& img, std::string& why,
+                            bool with_other = false) {
     img = Cls16Image();
     Side side[2];                                         // 0 src, 1 dst
     for (const SemRule& s : sem) {
@@ -1683,6 +1689,7 @@ static bool build_cls16_one(const std::vector<SemRule>& sem, uint32_t n_rules, C
     if (trie) img.src_mode = 2;
     Cls4Opts opt;
     opt.ext_src = hosts || trie;
+    opt.with_other = opt.lds_image_only = with_other;
     uint32_t rel_key[2] = {}, rel_val[2] = {};
     for (int sd = opt.ext_src ? 1 : 0; sd < 2; ++sd) {
         rel_key[sd] = uint32_t(opt.tail.size()) * 4;
@@ -1909,6 +1916,12 @@ bool build_pair4(const std::vector<SemRule>& sem, uint32_t n_rules, bool swap, C
     opt.with_other = true;
     if (!build_cls4_one(swap ? swap_sides(sem) : sem, n_rules, img, why, &opt)) return false;
     img.swap = swap ? 1 : 0;
+    return true;
+}
+
+bool build_pair16(const std::vector<SemRule>& sem, uint32_t n_rules, bool swap, Cls16Image& img, std::string& why) {
+    if (!build_cls16_one(swap ? swap_sides(sem) : sem, n_rules, img, why, true)) return false;
+    img.core.swap = swap ? 1 : 0;
     return true;
 }
 

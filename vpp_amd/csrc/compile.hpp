@@ -218,6 +218,12 @@ struct Cls4Opts {
     // classifies those connections with the others -- no OTHER queue, no
     // second image.  Its slots are its own (ctr_rule).
     bool with_other = false;
+    // The launch that stages this image counts nothing in LDS (the 16-byte
+    // pair launch, k16_pair.hip): a list mode fits when the image alone does
+    // (+ kLdsReserved within the budget), whatever its slot counters would take beside it.
+    // Without this the config-5 pair image fell from the sublists (124 KB,
+    // 80 KB of counters it never uses) to the template scan.
+    bool lds_image_only = false;
 };
 
 // The OTHER image of a rule set (in the main image's orientation: pass the
@@ -298,5 +304,12 @@ __host__ __device__ inline uint32_t fold6(uint32_t w0, uint32_t w1, uint32_t w2,
 // sem: semantic_rules(..., fam 0, ...) -- a packet's src and dst may be of
 // different families (Contains tests each address on its own).
 bool build_cls16(const std::vector<SemRule>& sem, uint32_t n_rules, Cls16Image& img, std::string& why);
+// The connection pair launch's image of `sem` (k16_pair.hip) in the
+// orientation `swap` (the main image's core.swap: the launch frames both
+// tuples once): the same front-end tables, a core of four cells per class
+// (Cls4Opts::with_other) with slots of its own (core.ctr_rule).  With
+// src_mode 1 and 2 the front end yields class rows for every protocol, so
+// protocols > 2 need no rep on this image.
+bool build_pair16(const std::vector<SemRule>& sem, uint32_t n_rules, bool swap, Cls16Image& img, std::string& why);
 
 }  // namespace cls

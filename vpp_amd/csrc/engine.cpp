@@ -277,6 +277,7 @@ static int table_compile(cls_engine* e, const char* name, const cls_rule* rules,
         if (!cls_kernel_exists(c.mode, c.list_mode, q.lds_resident, true))
             return fail(e, CLS_E_INVAL, "no 16-byte classify kernel for the compiled image (mode %u, list mode %u%s)",
                         c.mode, c.list_mode, q.lds_resident ? "" : ", global memory");
+        if (q.lds_resident) q.sem16 = std::make_shared<const std::vector<SemRule>>(std::move(s16));
     }
     out = std::move(t);
     return CLS_OK;
@@ -301,6 +302,7 @@ std::shared_ptr<Table> table_clone_host(const Table& s) {
     t->p16.lin = s.p16.lin;
     t->p16.oimg = s.p16.oimg;
     t->p16.lds_resident = s.p16.lds_resident;
+    t->p16.sem16 = s.p16.sem16;         // (as sem4)
     t->conn4 = s.conn4;
     t->conn16 = s.conn16;
     t->conn_bm = s.conn_bm;
@@ -558,6 +560,41 @@ static bool pair_image(cls_engine* e, Table& t) {
         }
     }
     return t.pimg_state > 0;
+}
+
+// The same for the 16-byte layout (Table::p16.pimg, compile.hpp build_pair16):
+// none when the four-cell image does not fit LDS beside 32 spare bytes, has
+// wide cells in global memory, or has no classify16_pair variant.
+static bool pair_image16(cls_engine* e, Table& t) {
+    auto& q = t.p16;
+    if (q.pimg_state == 0) {
+        q.pimg_state = -1;
+        std::string why;
+        const CompileScope scope(e->opts);
+        const Cls4Image& c = q.pimg.core;
+        if (q.ok && q.sem16 && build_pair16(*q.sem16, t.n_rules, q.img.core.swap != 0, q.pimg, why) &&
+            c.gcells.empty() && c.img_bytes + 32u <= uint32_t(max_lds_bytes()) &&
+            pair16_kernel_exists(c.mode, c.list_mode, q.pimg.src_mode) && upload(e, q.d_pimg, c) == CLS_OK) {
+            const std::vector<uint32_t>& m = c.ctr_rule;
+            if (q.d_pslot_rule.ensure(std::max<size_t>(1, m.size()) * 4) == hipSuccess &&
+                (m.empty() || hipMemcpy(q.d_pslot_rule.p, m.data(), m.size() * 4, hipMemcpyHostToDevice) == hipSuccess))
+                q.pimg_state = 1;
+            // ... and as u16 for the launch to stage in LDS beside the image
+            q.pslot16_n16 = 0;
+            if (q.pimg_state > 0 && t.n_rules < 0xFFFFu && !m.empty()) {
+                std::vector<uint16_t> m16((m.size() + 7) & ~size_t(7), 0);
+                for (size_t i = 0; i < m.size(); ++i) m16[i] = uint16_t(m[i]);
+                if (q.d_pslot16.ensure(m16.size() * 2) == hipSuccess &&
+                    hipMemcpy(q.d_pslot16.p, m16.data(), m16.size() * 2, hipMemcpyHostToDevice) == hipSuccess)
+                    q.pslot16_n16 = uint32_t(m16.size() / 8);
+            }
+        }
+        if (q.pimg_state < 0) {
+            q.pimg = Cls16Image();
+            (void)hipGetLastError();
+        }
+    }
+    return q.pimg_state > 0;
 }
 
 // Packets in an image's frame: src and dst exchanged for a destination-keyed one.
@@ -1622,9 +1659,17 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     // word's counter index (descriptor counter base + the slot's rule)
     // instead of its slot: the connection kernel then counts a large-ACL call
     // without a descriptor read and a dependent slot -> rule gather.
-    auto pair_ok = [&](const Table& t) {
+    // A 16-byte batch takes its pair launch (classify16_pair) on the table's
+    // pair image alone -- there is no OTHER-queue form of it -- so the table
+    // qualifies only with that image (built here, at the first batch that
+    // could take it); its loads need the addresses 16-B aligned and 32-bit
+    // byte offsets into them (option conn_pair16=0: the two slot launches).
+    auto pair_ok = [&](Table& t) {
+        if (k16)
+            return t.p16.ok && t.p16.lds_resident && aligned(src, 16) && aligned(dst, 16) && n <= (1ull << 28) &&
+                   e->opts.conn_pair && e->opts.conn_pair16 && pair_image16(e, t);
         const uint32_t *s4 = static_cast<const uint32_t*>(src), *d4 = static_cast<const uint32_t*>(dst);
-        return !k16 && t.lds_resident && aligned(s4, 16) && aligned(d4, 16) && aligned(dp, 8) && aligned(sp, 8) &&
+        return t.lds_resident && aligned(s4, 16) && aligned(d4, 16) && aligned(dp, 8) && aligned(sp, 8) &&
                aligned(pr, 4) && e->opts.conn_pair;
     };
     bool all_pair = !big.empty();
@@ -1719,6 +1764,32 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
                     HIPC(e, launch_classify4_slots(cd, syn, pre, t.lds_resident, cfg));
                     HIPC(e, launch_classify4_slots(cd, ack, pre + stride, t.lds_resident, cfg));
                 }
+            } else if (pair_ok(t) && (!count || pre_rules)) {
+                // 16-byte layout: both tuples on the pair image in one launch
+                // (k16_pair.hip), written as the IPv4 pair launch writes them
+                auto& q = t.p16;
+                const Cls4Image& pi = q.pimg.core;
+                const Cls4Dev pd = cls4_dev(pi, q.d_pimg, DevBuf(), 0, t.n_rules);
+                PairMap sm;
+                sm.srl = (pi.img_bytes + 15u) & ~15u;
+                if (pre_rules && q.pslot16_n16 && e->opts.pair_map_lds &&
+                    sm.srl + 16u * q.pslot16_n16 + 32u <= uint32_t(max_lds_bytes())) {
+                    sm.map = q.d_pslot16.as<uint16_t>();
+                    sm.n16 = q.pslot16_n16;
+                } else {
+                    sm.srl = 0;
+                }
+                cfg.grid = cls_grid(e, true, true, sm.srl ? sm.srl + 16u * sm.n16 : pi.img_bytes, n);
+                if (e->opts.debug_conn)
+                    std::fprintf(stderr, "pair16: pimg %u mode %u list mode %u fe %u map %u (img %u oimg %u) grid %d step %u\n",
+                                 pi.img_bytes, pi.mode, pi.list_mode, q.pimg.src_mode, 16u * sm.n16,
+                                 q.img.core.img_bytes, q.oimg.img_bytes, cfg.grid, 64u * kPair16Conns);
+                const uint4 *s16 = static_cast<const uint4*>(src), *d16 = static_cast<const uint4*>(dst);
+                Pkts16 pk{s16, d16, dp, pr, n, 0u};
+                if (pi.swap) std::swap(pk.src, pk.dst);       // destination-keyed image
+                HIPC(e, launch_classify16_pair(pd, fe16(q.pimg, DevBuf()), pk, sp, pre, stride,
+                                               pre_rules ? q.d_pslot_rule.as<uint32_t>() : nullptr,
+                                               desc[big[b]].ctr_off, pre_bytes, sm, cfg));
             } else {
                 auto& q = t.p16;
                 const Cls4Image& ci = q.img.core;
@@ -1732,6 +1803,9 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
                     std::swap(syn.src, syn.dst);
                     std::swap(ack.src, ack.dst);
                 }
+                if (e->opts.debug_conn)
+                    std::fprintf(stderr, "slots16: img %u mode %u list mode %u fe %u lds %d pimg state %d\n", ci.img_bytes,
+                                 ci.mode, ci.list_mode, q.img.src_mode, int(q.lds_resident), q.pimg_state);
                 HIPC(e, launch_classify16_slots(cd, fe, syn, pre, q.lds_resident, cfg));
                 HIPC(e, launch_classify16_slots(cd, fe, ack, pre + stride, q.lds_resident, cfg));
             }
@@ -2317,6 +2391,14 @@ int cls_compile_v16(const cls_rule* rules, uint32_t n, void* blob, uint64_t cap,
     Cls16Image img;
     Cls4Image oimg;
     if (!build_cls16(sem, n, img, why) || !build_other4(img.sem, n, oimg, why)) return CLS_E_INVAL;
+    if (o.pair4) {
+        // (option pair4: the connection pair launch's four-cell image, in the
+        // main image's orientation, instead; no OTHER image -- CPU tests of
+        // that compile)
+        Cls16Image pimg;
+        if (!build_pair16(sem, n, img.core.swap != 0, pimg, why)) return CLS_E_INVAL;
+        img = std::move(pimg);
+    }
     cls_image_v16_header h16;
     std::memset(&h16, 0, sizeof h16);
     for (int sd = 0; sd < 2; ++sd) {
@@ -2338,7 +2420,7 @@ int cls_compile_v16(const cls_rule* rules, uint32_t n, void* blob, uint64_t cap,
     const size_t extra = sizeof h16 - sizeof h16.core;
     return write_blob(&img.core, linear4(img.sem), n, 0x434C3136u, reinterpret_cast<const uint8_t*>(&h16) + sizeof h16.core,
                       extra, blob, cap, need, img.src_mode >= 1 ? &img.src_search : nullptr,
-                      offsetof(cls_image_v16_header, off_src_search) - sizeof h16.core, &oimg);
+                      offsetof(cls_image_v16_header, off_src_search) - sizeof h16.core, o.pair4 ? nullptr : &oimg);
 }
 
 }  // extern "C"

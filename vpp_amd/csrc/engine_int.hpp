@@ -130,6 +130,17 @@ struct Table {
         DevBuf d_src_search;       // src_mode 1, 2: the source interval table (global memory)
         bool lds_resident = false;
         DevBuf d_slot_rule;        // slot mode (connection batches): slot -> rule, core then OTHER image
+        // The pair launch's image (compile.hpp build_pair16: a fourth cell
+        // per class in the core), built from sem16 (the fam-0 rules, kept for
+        // LDS-resident tables) at the table's first connection batch that
+        // can take the launch, with its own slot -> rule map as u32 and as
+        // u16 (pslot16_n16 16-B units): the states and buffers of
+        // Table::pimg
+        std::shared_ptr<const std::vector<SemRule>> sem16;
+        int pimg_state = 0;
+        Cls16Image pimg;
+        DevBuf d_pimg, d_pslot_rule, d_pslot16;
+        uint32_t pslot16_n16 = 0;
     } p16;
     // connection path: compact linear rules (cls_connect_batch's rule pool),
     // slot -> rule of the v4 images (slot mode), and the per-rule connection

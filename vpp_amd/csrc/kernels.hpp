@@ -232,6 +232,29 @@ inline uint64_t pair_queue_words(uint64_t n, int grid) {
     return 4ull * kPairBlock * ((nsteps + nthreads - 1) / nthreads);
 }
 
+// Both tuples of a 16-byte connection batch in one launch (k16_pair.hip) on
+// the table's pair image (compile.hpp build_pair16: four cells per class,
+// LDS-resident, no wide cells; fe: its front end): the SYN tuple (p.src,
+// p.dst, p.dport) and the SYN-ACK tuple (p.dst, p.src, sport), written as
+// launch_classify4_pair writes them (out, stride, slot_rule, ctr_base,
+// wbytes, sm as there; slots are the pair image's own).  A destination-keyed
+// image takes p.src and p.dst exchanged.  Needs 16-B aligned src / dst, 4-B
+// aligned out, p.n <= 2^28 (32-bit byte offsets into the address arrays).
+// Whole wave-steps of 64 x kPair16Conns connections take the vector path
+// (lane l of a wave: base + 64 k + l), the rest a per-connection tail.
+constexpr uint32_t kPair16Conns = 2;   // connections per lane per step
+// ... and whether it has a variant for a core of source lookup `mode` and
+// `list_mode` behind source front end `src_mode` (Cls16Image): list modes
+// 0-4 (an image with wide cells, 5 and 6, never takes the launch)
+inline bool pair16_kernel_exists(uint32_t mode, uint32_t list_mode, uint32_t src_mode) {
+    if (list_mode > 4 || src_mode > 2) return false;
+    if (src_mode) return mode == 3;
+    return mode == 0 || mode == 1 || (mode == 4 && list_mode >= 3);
+}
+hipError_t launch_classify16_pair(const Cls4Dev& t, const Fe16& fe, const Pkts16& p, const uint16_t* sport,
+                                  uint32_t* out, uint64_t stride, const uint32_t* slot_rule, uint32_t ctr_base,
+                                  uint32_t wbytes, const PairMap& sm, const LaunchCfg& cfg);
+
 struct ConnDesc {                // one bound ACL for the connection kernel
     uint32_t rule_off;           // linear ACLs: first rule in the call's rule pool
     uint32_t n;                  // linear rules

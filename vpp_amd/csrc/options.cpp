@@ -66,6 +66,7 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
     OPT("fold_split", fold_split, b)
     OPT("conn_bitmap", conn_bitmap, b)
     OPT("conn_pair", conn_pair, b)
+    OPT("conn_pair16", conn_pair16, b)
     OPT("conn_pre_rules", conn_pre_rules, b)
     OPT("conn_pre_narrow", conn_pre_narrow, b)
     OPT("pair_other_global", pair_other_global, b)

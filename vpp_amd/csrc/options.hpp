@@ -28,7 +28,7 @@ struct Opts {
     int v16_src_trie = -1;      // 16-byte front end: 1 the source trie, 0 never
     int orient = -1;            // 0 source-keyed, 1 destination-keyed (-1: the better one)
     bool debug_modes = false;   // stderr: why a list mode was refused
-    bool pair4 = false;         // cls_compile_v4: the connection pair launch's four-cell image (tests)
+    bool pair4 = false;         // cls_compile_v4 / v16: the connection pair launch's four-cell image (tests)
     // ---- classify launches (engine.cpp) -----------------------------------
     uint32_t other_cap = 0;     // OTHER queue entries per workgroup (0: sized by the batch)
     int wg_per_cu = 0;          // classify workgroups per CU (0: by LDS)
@@ -37,6 +37,7 @@ struct Opts {
     // ---- connection batches (engine.cpp) ----------------------------------
     bool conn_bitmap = true;    // bitmap form of linear IPv4 ACLs
     bool conn_pair = true;      // both tuples of a large ACL in one launch (classify4_pair)
+    bool conn_pair16 = true;    // ... of a 16-byte batch too, on the table's pair image (classify16_pair)
     bool conn_pre_rules = true; // counting: the pair launch writes counter indices, not slots
     bool conn_pre_narrow = true;// u8 results / u16 words where they fit (else u32 words)
     uint32_t pair_qcap = 0;     // pair launch: OTHER queue entries per wave (0: sized by the batch)
