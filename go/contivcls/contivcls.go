@@ -455,9 +455,35 @@ func (en *Engine) resolve(c *Conn) (srcIf, dstIf string, srcIP, dstIP net.IP, ok
 // Go's To4).  count: add every evalACL call's terminating rule to the tables'
 // connection counters (cls_conn_counters).
 func (en *Engine) ConnectionBatch(calls []Conn, count bool) ([]aclengine.ConnectionAction, error) {
+	out, _, err := en.connections(calls, count, false)
+	return out, err
+}
+
+// ConnectRules is ConnectionBatch with the trace (cls_connect_rules): besides
+// every call's ConnectionAction, the rule at which each of testConnection's
+// four evalACL calls ended -- what the reference logs per call
+// (aclengine_mock.go:651-654) -- in its order: SYN through the source
+// interface's inbound ACL, SYN through the destination's outbound, SYN-ACK
+// through the destination's inbound, SYN-ACK through the source's outbound.
+// Each entry is the rule's index in that ACL (GetInboundACL / GetOutboundACL
+// of the interface), len(Rules) for the default DENY, or -1 when
+// testConnection does not make the call or makes it on a nil ACL; a call that
+// fails before testConnection has four -1.  No counters are touched.
+func (en *Engine) ConnectRules(calls []Conn) ([]aclengine.ConnectionAction, [][4]int32, error) {
+	return en.connections(calls, false, true)
+}
+
+func (en *Engine) connections(calls []Conn, count bool, trace bool) ([]aclengine.ConnectionAction, [][4]int32, error) {
 	en.Lock()
 	defer en.Unlock()
 	out := make([]aclengine.ConnectionAction, len(calls))
+	var rules [][4]int32
+	if trace {
+		rules = make([][4]int32, len(calls))
+		for i := range rules {
+			rules[i] = [4]int32{-1, -1, -1, -1}
+		}
+	}
 	var idx []int
 	var sif, dif []uint32
 	var sip, dip []net.IP
@@ -491,11 +517,15 @@ func (en *Engine) ConnectionBatch(calls []Conn, count bool) ([]aclengine.Connect
 	}
 	n := len(idx)
 	if n == 0 {
-		return out, nil
+		return out, rules, nil
 	}
 	// every slice goes to the shim as its own pointer (pointer-free Go
 	// memory); the shim builds cls_conn_soa on the C stack
 	res := make([]uint8, n)
+	var tr []int32 // the trace: four rules per evaluated connection
+	if trace {
+		tr = make([]int32, 4*n)
+	}
 	flags := C.uint32_t(0)
 	if count {
 		flags |= C.CLS_F_COUNT
@@ -508,30 +538,45 @@ func (en *Engine) ConnectionBatch(calls []Conn, count bool) ([]aclengine.Connect
 			s4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
 			d4[k] = uint32(b[0])<<24 | uint32(b[1])<<16 | uint32(b[2])<<8 | uint32(b[3])
 		}
-		rc = C.clsg_connect_v4(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint32_t)(&s4[0]),
-			(*C.uint32_t)(&d4[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
-			C.uint64_t(n), (*C.uint8_t)(&res[0]), flags)
+		if trace {
+			rc = C.clsg_connect_rules_v4(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint32_t)(&s4[0]),
+				(*C.uint32_t)(&d4[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
+				C.uint64_t(n), (*C.uint8_t)(&res[0]), (*C.int32_t)(&tr[0]), flags)
+		} else {
+			rc = C.clsg_connect_v4(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint32_t)(&s4[0]),
+				(*C.uint32_t)(&d4[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
+				C.uint64_t(n), (*C.uint8_t)(&res[0]), flags)
+		}
 	} else {
 		s16, d16 := make([]byte, 16*n), make([]byte, 16*n)
 		for k := 0; k < n; k++ {
 			a, b := sip[k].To16(), dip[k].To16()
 			if a == nil || b == nil {
-				return nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+				return nil, nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
 			}
 			copy(s16[16*k:], a)
 			copy(d16[16*k:], b)
 		}
-		rc = C.clsg_connect_v16(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint8_t)(&s16[0]),
-			(*C.uint8_t)(&d16[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
-			C.uint64_t(n), (*C.uint8_t)(&res[0]), flags)
+		if trace {
+			rc = C.clsg_connect_rules_v16(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint8_t)(&s16[0]),
+				(*C.uint8_t)(&d16[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
+				C.uint64_t(n), (*C.uint8_t)(&res[0]), (*C.int32_t)(&tr[0]), flags)
+		} else {
+			rc = C.clsg_connect_v16(en.e, (*C.uint32_t)(&sif[0]), (*C.uint32_t)(&dif[0]), (*C.uint8_t)(&s16[0]),
+				(*C.uint8_t)(&d16[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), (*C.uint8_t)(&proto[0]),
+				C.uint64_t(n), (*C.uint8_t)(&res[0]), flags)
+		}
 	}
 	if rc != C.CLS_OK {
-		return nil, en.lastErr()
+		return nil, nil, en.lastErr()
 	}
 	for k, i := range idx {
 		out[i] = aclengine.ConnectionAction(res[k])
+		if trace {
+			copy(rules[i][:], tr[4*k:4*k+4])
+		}
 	}
-	return out, nil
+	return out, rules, nil
 }
 
 // ConnectionPodToPod replaces MockACLEngine.ConnectionPodToPod (:243-300).

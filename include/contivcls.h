@@ -346,6 +346,27 @@ int cls_stream_floor_conn(cls_engine* e, const cls_conn_soa* conns, uint64_t n, 
 int cls_connect_batch(cls_engine* e, const cls_conn_soa* conns, uint64_t n,
                       uint8_t* conn_verdict_out, uint32_t flags, void* stream);
 
+/* The trace twin of cls_connect_batch: besides the ConnectionAction (as
+ * there; conn_verdict_out may be NULL), the rule at which every evalACL call
+ * of testConnection ended -- what the reference logs per call (:651-654).
+ * rule_out[4 i + k] is the k-th call of connection i in testConnection's
+ * order: k = 0 SYN through src_if's inbound ACL, 1 SYN through dst_if's
+ * outbound, 2 SYN-ACK through dst_if's inbound, 3 SYN-ACK through src_if's
+ * outbound.  Each entry is the rule's index in that ACL's table, R for the
+ * default DENY (:667), or -1 when testConnection does not make the call or
+ * makes it on a nil ACL.  The tables are those of the bindings snapshotted at
+ * the call: cls_if_acls(src_if / dst_if) names them (in_table for k = 0 and
+ * 2, out_table for k = 1 and 3).  A device batch's connection with an unknown
+ * interface id gives CLS_CONN_FAILURE and four -1 (a host batch is rejected
+ * with CLS_E_INVAL).  Flags: CLS_F_DEVICE (device arrays, rule_out 16-byte
+ * aligned, stream-ordered like cls_connect_batch; a host batch returns with
+ * the results), CLS_F_CONN_CLS and CLS_F_FORCE_LINEAR as there; CLS_F_COUNT
+ * is CLS_E_INVAL: the trace touches no counters.  At most 2^30 connections
+ * per call. */
+int cls_connect_rules(cls_engine* e, const cls_conn_soa* conns, uint64_t n,
+                      uint8_t* conn_verdict_out, int32_t* rule_out,
+                      uint32_t flags, void* stream);
+
 /* Per-(ACL, rule) hit counters of the connection path: counters_out[k]
  * (k < R) = evalACL calls of cls_connect_batch (CLS_F_COUNT) on this table that
  * terminated at rule k, counters_out[R] = calls that fell through to the

@@ -115,6 +115,44 @@ static inline int clsg_connect_v16(cls_engine* e, const uint32_t* src_if, const 
     return cls_connect_batch(e, &c, n, out, flags, NULL);
 }
 
+/* cls_connect_rules of IPv4 connections: the ConnectionAction (out, may be
+ * NULL) and the four evalACL calls' terminating rules (rules[4 i + k], -1: no
+ * call) per connection. */
+static inline int clsg_connect_rules_v4(cls_engine* e, const uint32_t* src_if, const uint32_t* dst_if,
+                                        const uint32_t* src4, const uint32_t* dst4, const uint16_t* sport,
+                                        const uint16_t* dport, const uint8_t* proto, uint64_t n, uint8_t* out,
+                                        int32_t* rules, uint32_t flags) {
+    cls_conn_soa c;
+    memset(&c, 0, sizeof c);
+    c.pkt.af = CLS_AF_V4;
+    c.pkt.src4 = src4;
+    c.pkt.dst4 = dst4;
+    c.pkt.sport = sport;
+    c.pkt.dport = dport;
+    c.pkt.proto = proto;
+    c.src_if = src_if;
+    c.dst_if = dst_if;
+    return cls_connect_rules(e, &c, n, out, rules, flags, NULL);
+}
+
+/* cls_connect_rules of 16-byte connections. */
+static inline int clsg_connect_rules_v16(cls_engine* e, const uint32_t* src_if, const uint32_t* dst_if,
+                                         const uint8_t* src16, const uint8_t* dst16, const uint16_t* sport,
+                                         const uint16_t* dport, const uint8_t* proto, uint64_t n, uint8_t* out,
+                                         int32_t* rules, uint32_t flags) {
+    cls_conn_soa c;
+    memset(&c, 0, sizeof c);
+    c.pkt.af = CLS_AF_V16;
+    c.pkt.src16 = src16;
+    c.pkt.dst16 = dst16;
+    c.pkt.sport = sport;
+    c.pkt.dport = dport;
+    c.pkt.proto = proto;
+    c.src_if = src_if;
+    c.dst_if = dst_if;
+    return cls_connect_rules(e, &c, n, out, rules, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -17,7 +17,13 @@ around the locals' prefixes); the same line, 46 algorithmic bytes per
 connection.  The connection stream floor is IPv4 only: the 16-byte line
 reports the 16-byte classify stream's floor (35 B read, 1 B written per
 packet) beside the 37 + 1 B of a pair launch (k16_pair.hip).
-usage: python tools/conn_bench.py [--n 4194304] [--iters 5] [--locals 64] [--af 4|16]
+--trace: also times cls_connect_rules (the per-call matched-rule trace: 16 B
+written per connection beside the verdict byte) on the same device batch, and
+reports for the plain, the counted and the trace batch the GPU time of one
+batch's launches (device events around a call on a stream of its own) beside
+the back-to-back wall time -- "trace" in the JSON line; its rows are checked
+against orc_test_connection_hits on the CPU sample.
+usage: python tools/conn_bench.py [--n 4194304] [--iters 5] [--locals 64] [--af 4|16] [--trace]
 """
 import argparse
 import json
@@ -76,6 +82,57 @@ def traffic16(n, pool, spec, half, rng):
     return tr
 
 
+def trace_times(a, eng, dargs, n):
+    """--trace: the plain, counted and trace batch of the same device
+    connections through the ABI on one build: ms per batch back to back (wall
+    time over a.iters calls, one wait at the end) and the GPU time of one
+    batch's launches (device events around each of a.iters calls on a stream
+    of the tool's own; median)."""
+    import ctypes as C
+
+    import torch
+    from vpp_amd import _abi
+    from vpp_amd.engine import _ptr
+    out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    rules = torch.full((n, 4), -2, dtype=torch.int32, device="cuda")
+    if a.af == 16:
+        pk = _abi.PktSoa(_abi.AF_V16, None, None, _ptr(dargs[2]), _ptr(dargs[3]), _ptr(dargs[5]), _ptr(dargs[6]),
+                         _ptr(dargs[4]))
+    else:
+        pk = _abi.PktSoa(_abi.AF_V4, _ptr(dargs[2]), _ptr(dargs[3]), None, None, _ptr(dargs[5]), _ptr(dargs[6]),
+                         _ptr(dargs[4]))
+    cs = _abi.ConnSoa(pk, _ptr(dargs[0]), _ptr(dargs[1]))
+    L, h, csr, op, rp = _abi.lib(), eng.h, C.byref(cs), _ptr(out), _ptr(rules)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    calls = {"plain": lambda s: L.cls_connect_batch(h, csr, n, op, _abi.F_DEVICE, s),
+             "counted": lambda s: L.cls_connect_batch(h, csr, n, op, _abi.F_DEVICE | _abi.F_COUNT, s),
+             "trace": lambda s: L.cls_connect_rules(h, csr, n, op, rp, _abi.F_DEVICE, s)}
+    res = {}
+    for kind, fn in calls.items():
+        assert fn(None) == 0                                 # warm: the kind's plan and uploads
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.iters):
+            assert fn(None) == 0
+        torch.cuda.synchronize()
+        piped = (time.perf_counter() - t0) / a.iters
+        assert fn(sp) == 0
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+        for e0, e1 in evs:
+            e0.record(stream)
+            assert fn(sp) == 0
+            e1.record(stream)
+            stream.synchronize()
+        res[kind] = {"abi_pipelined_ms_per_batch": round(piped * 1e3, 4),
+                     "gpu_ms_per_batch": round(float(np.median([e0.elapsed_time(e1) for e0, e1 in evs])), 4)}
+    res["bytes_written_per_connection"] = {"plain": 1, "counted": 1, "trace": 17}
+    res["rows"] = rules.cpu().numpy()
+    assert (res["rows"] >= -1).all()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 22)
@@ -87,6 +144,7 @@ def main():
     ap.add_argument("--locals", type=int, default=64)
     ap.add_argument("--count", type=int, default=1)
     ap.add_argument("--af", type=int, default=4, choices=[4, 16], help="16: mixed-family batches (CLS_AF_V16)")
+    ap.add_argument("--trace", action="store_true", help="time cls_connect_rules beside the plain and counted batches")
     ap.add_argument("--no-check", action="store_true", help="diagnostic builds: skip the parity asserts")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="library tuning switch (cls_engine_set_option), repeatable")
@@ -220,12 +278,22 @@ def main():
                 "achieved": round(22 * n / abi_piped / 1e9, 1), "frac": round(22 * n / abi_piped / 8e12, 4),
                 "stream_floor_ms": round(floor, 4), "frac_of_stream_floor": round(floor / (abi_piped * 1e3), 4),
                 "timed": "abi_pipelined_ms_per_batch"}
+    trace = None
+    if a.trace:
+        trace = trace_times(a, eng, dargs, n)
     k = a.cpu_sample
     t1 = time.perf_counter()
     want, _ = oracle_connections(bind, by_name, ifs, si[:k], di[:k], {f: v[:k] for f, v in tr.items()}, a.af)
     cpu_dt = time.perf_counter() - t1
     if not a.no_check:
         assert np.array_equal(out[:k], want), "connection verdicts differ from the oracle"
+    if trace is not None:
+        rows = trace.pop("rows")
+        if not a.no_check:
+            from test_connect_trace_cpu import oracle_rows
+            wv, wr = oracle_rows(bind, by_name, ifs, si[:k], di[:k], {f: v[:k] for f, v in tr.items()}, a.af)
+            assert np.array_equal(wv, want) and np.array_equal(rows[:k], wr), "trace rows differ from the oracle"
+            trace["parity"] = "first %d rows bit-exact vs orc_test_connection_hits" % k
     # the CPU baseline: the fast port (rules pre-parsed, orc_connect_fast)
     # over OpenMP on the cores this process may use, on a prefix of the batch
     import oracle
@@ -257,7 +325,7 @@ def main():
         "hbm_resident": {"value": round(n / dev_dt / 1e6, 3), "unit": "Mconn/s",
                          "ms_per_batch": round(dev_dt * 1e3, 4), "abi_ms_per_batch": round(abi_dt * 1e3, 4),
                          "abi_pipelined_ms_per_batch": round(abi_piped * 1e3, 4)},
-        "roofline": roof,
+        "roofline": roof, **({"trace": trace} if trace is not None else {}),
         "linear_scan": {"value": round(n / res["linear"][0] / 1e6, 3), "unit": "Mconn/s",
                         "ms_per_batch": round(res["linear"][0] * 1e3, 3)},
         "verdicts": np.bincount(out, minlength=4).tolist(),

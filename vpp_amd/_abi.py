@@ -49,7 +49,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_table_put", "cls_table_del", "cls_table_get_info", "cls_classify", "cls_classify_rules",
            "cls_last_kernel_ms", "cls_kernel_times", "cls_kernel_starts", "cls_kernel_times_reset", "cls_acl_put", "cls_acl_del", "cls_acl_table", "cls_acl_counts",
            "cls_if_id",
-           "cls_if_acls", "cls_connect_batch", "cls_gen_traffic_v4", "cls_compile_v4", "cls_image_kernel",
+           "cls_if_acls", "cls_connect_batch", "cls_connect_rules", "cls_gen_traffic_v4", "cls_compile_v4", "cls_image_kernel",
            "cls_compile_v16", "cls_gen_traffic_v16", "cls_stream_floor", "cls_stream_floor_shapes", "cls_stream_floor_conn", "cls_conn_bitmap_eval", "cls_conn_counters",
            "cls_acl_stats", "cls_engine_devices", "cls_device_engine", "cls_shard_range", "cls_batch_create",
            "cls_batch_destroy", "cls_batch_shards", "cls_batch_shard", "cls_batch_field", "cls_batch_mirror",
@@ -151,7 +151,9 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise ClsError("libcontivcls.so not built (run __graft_entry__.build() or "
                        "make -C vpp_amd/csrc); the product has no CPU fallback")
-    _lib = bind(LIB_PATH)
+    # (CONTIVCLS_LIB, A/B timing: the other build may be an older one, without
+    # the newest entry points)
+    _lib = bind(LIB_PATH, strict=not os.environ.get("CONTIVCLS_LIB"))
     return _lib
 
 
@@ -200,6 +202,7 @@ def bind(path: str, strict: bool = True):
         "cls_if_id": (C.c_int, [vp, C.c_char_p, C.POINTER(u32)]),
         "cls_if_acls": (C.c_int, [vp, u32, C.POINTER(i32), C.POINTER(i32)]),
         "cls_connect_batch": (C.c_int, [vp, C.POINTER(ConnSoa), u64, vp, u32, vp]),
+        "cls_connect_rules": (C.c_int, [vp, C.POINTER(ConnSoa), u64, vp, vp, u32, vp]),
         "cls_conn_counters": (C.c_int, [vp, u32, vp, u32]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,

@@ -1423,6 +1423,17 @@ int cls_connect_batch(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t*
     return connect_locked(e, c, n, out, flags, stream, false);
 }
 
+int cls_connect_rules(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* out, int32_t* rule_out,
+                      uint32_t flags, void* stream) {
+    if (!e || !c || (n && !rule_out)) return CLS_E_INVAL;
+    if (flags & CLS_F_COUNT) return fail(e, CLS_E_INVAL, "cls_connect_rules does not count (CLS_F_COUNT)");
+    if ((flags & CLS_F_DEVICE) && n && !aligned(rule_out, 16))
+        return fail(e, CLS_E_INVAL, "device rule_out must be 16-byte aligned");
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    return connect_locked(e, c, n, out, flags, stream, false, rule_out);
+}
+
 }  // extern "C"
 
 // The OTHER queue of a pair launch: a fixed segment per workgroup (its
@@ -1435,7 +1446,7 @@ static uint32_t pair_qcap(const cls_engine* e, uint64_t n, int grid) {
 }
 
 int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* out, uint32_t flags, void* stream,
-                   bool sync) {
+                   bool sync, int32_t* rule_out) {
     const cls_pkt_soa& pk = c->pkt;
     const bool k16 = pk.af == CLS_AF_V16;
     if (!k16 && pk.af != CLS_AF_V4) return fail(e, CLS_E_INVAL, "af must be CLS_AF_V4 or CLS_AF_V16");
@@ -1444,6 +1455,9 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     if (n && (!src || !dst || !pk.sport || !pk.dport || !pk.proto || !c->src_if || !c->dst_if))
         return fail(e, CLS_E_INVAL, "missing connection arrays");
     const bool dev = flags & CLS_F_DEVICE, count = flags & CLS_F_COUNT;
+    // the trace (cls_connect_rules): the calls' rules, no counters; it needs
+    // the large ACLs' rule-bearing words as a counting batch does
+    const bool trace = rule_out != nullptr, rules_wanted = count || trace;
     const size_t ab = k16 ? 16 : 4;                       // address bytes
     // the kernels index connections with 32-bit offsets
     if (n > kClsChunk) return fail(e, CLS_E_INVAL, "connection batch above 2^30 connections");
@@ -1490,6 +1504,14 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
         sif = e->s_if_a.as<uint32_t>(); dif = e->s_if_b.as<uint32_t>();
         sp = e->s_sport.as<uint16_t>(); dp = e->s_dport.as<uint16_t>();
         pr = e->s_proto.as<uint8_t>(); o = e->s_verdict.as<uint8_t>();
+    } else if (!o && n) {                                 // a trace without verdicts: the kernel's byte goes to scratch
+        HIPC(e, grow(e->s_verdict, n));
+        o = e->s_verdict.as<uint8_t>();
+    }
+    int32_t* ro = rule_out;
+    if (trace && !dev && n) {
+        HIPC(e, grow(e->s_trace, n * 16));
+        ro = e->s_trace.as<int32_t>();
     }
     // The plan (ConnPlan): a device batch reuses the last one while the
     // bindings and the flags are the same; a host batch picks its large ACLs
@@ -1497,7 +1519,8 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     const bool use_big = n && !(flags & CLS_F_FORCE_LINEAR) && (n >= kConnClsMinBatch || (flags & CLS_F_CONN_CLS));
     const bool use_bm = !k16 && n && !(flags & CLS_F_FORCE_LINEAR) && e->opts.conn_bitmap;
     const uint64_t key = uint64_t(k16) | uint64_t(count) << 1 | uint64_t(use_big) << 2 |
-                         uint64_t((flags & CLS_F_CONN_CLS) != 0) << 3 | uint64_t(use_bm) << 4;
+                         uint64_t((flags & CLS_F_CONN_CLS) != 0) << 3 | uint64_t(use_bm) << 4 |
+                         uint64_t(trace) << 5;
     ConnPlan fresh;
     ConnPlan& P = dev ? e->conn_plan : fresh;
     const bool planned = dev && P.gen == e->conn_gen && P.key == key;
@@ -1674,10 +1697,10 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     };
     bool all_pair = !big.empty();
     for (uint32_t b : big) all_pair = all_pair && pair_ok(*dtab[b]);
-    const bool pre_rules = count && all_pair && e->opts.conn_pre_rules;
+    const bool pre_rules = rules_wanted && all_pair && e->opts.conn_pre_rules;
     // ... and a batch that does not count needs only the ACLActions: one byte
     // per connection for both tuples (the words would be 8 B)
-    const bool pre_res8 = !count && all_pair && e->opts.conn_pre_narrow;
+    const bool pre_res8 = !rules_wanted && all_pair && e->opts.conn_pre_narrow;
     // ... and a counting one u16 words when every counter index fits 14 bits
     const uint32_t pre_bytes = pre_res8 ? 1u : pre_rules && P.n_ctr <= (1u << 14) &&
                                                        e->opts.conn_pre_narrow ? 2u : 4u;
@@ -1697,7 +1720,7 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
                 // Both tuples in one launch when the image is LDS-resident and
                 // the arrays allow 16-B loads; the OTHER image beside the main
                 // one when both fit (no slot counters in this mode)
-                if (pair_ok(t) && e->opts.pair_o4 && (!count || pre_rules) && pair_image(e, t)) {
+                if (pair_ok(t) && e->opts.pair_o4 && (!rules_wanted || pre_rules) && pair_image(e, t)) {
                     // the pair image: protocols > 2 in the main loop with the
                     // others -- no OTHER queue, drain or second image (its
                     // slots are its own: counting takes the counter-index
@@ -1764,7 +1787,7 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
                     HIPC(e, launch_classify4_slots(cd, syn, pre, t.lds_resident, cfg));
                     HIPC(e, launch_classify4_slots(cd, ack, pre + stride, t.lds_resident, cfg));
                 }
-            } else if (pair_ok(t) && (!count || pre_rules)) {
+            } else if (pair_ok(t) && (!rules_wanted || pre_rules)) {
                 // 16-byte layout: both tuples on the pair image in one launch
                 // (k16_pair.hip), written as the IPv4 pair launch writes them
                 auto& q = t.p16;
@@ -1817,6 +1840,7 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     a.n_ctr = count ? n_ctr : 0;
     a.src_if = sif; a.dst_if = dif; a.src = src; a.dst = dst;
     a.sport = sp; a.dport = dp; a.proto = pr; a.n = n; a.out = o;
+    a.rule_out = ro;
     // LDS: the rule pool first (every evaluation step reads it), then the u32
     // counters if they fit beside it; otherwise global-memory variants
     // (option conn_no_lds, tests: bit 0 rules from global memory, bit 1
@@ -1988,11 +2012,13 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
         size_t nbm = 0;
         for (const ConnDesc& d : desc) nbm += d.bm_off != 0xFFFFFFFFu;
         std::fprintf(stderr, "connect: n %llu desc %zu big %zu bitmaps %zu pool %zu lds_rules %d ctr %u cmode %d "
-                     "meta %s jobs %s lds %zu ctr16 %u per_cu %d block %d grid %llu bm_steps %u\n", (unsigned long long)n,
+                     "meta %s jobs %s lds %zu ctr16 %u per_cu %d block %d grid %llu bm_steps %u trace %d pre_rules %d "
+                     "pre_bytes %u\n", (unsigned long long)n,
                      desc.size(), big.size(), nbm, pool.size(), int(lds_rules), n_ctr, cmode,
                      a.meta_lds != 0xFFFFFFFFu ? "lds" : "global", a.job_lds != 0xFFFFFFFFu ? "lds" : "shuffle",
                      lds,
-                     a.ctr16, per_cu, block, (unsigned long long)grid, P.bm_steps);
+                     a.ctr16, per_cu, block, (unsigned long long)grid, P.bm_steps, int(trace), int(pre_rules),
+                     big.empty() ? 0u : pre_bytes);
     }
     // LDS counters leave the launch as one row per workgroup, summed into the
     // tables' counters by the rows launch (option conn_flush_atomic: device
@@ -2004,7 +2030,7 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
         HIPC(e, grow(e->s_crows, size_t(grid) * nw * 4));
         a.ctr_rows = e->s_crows.as<uint32_t>();
     }
-    HIPC(e, launch_connect(a, k16, lds_rules, cmode, int(grid), block, lds, s));
+    HIPC(e, launch_connect(a, k16, lds_rules, trace ? 3 : cmode, int(grid), block, lds, s));
     if (cmode && n) {
         uint32_t max_rules = 0;
         for (const ConnDesc& d : desc) max_rules = std::max(max_rules, d.n_rules);
@@ -2040,7 +2066,8 @@ int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* ou
     } else if (cmode) {
         e->cctr_zero = true;            // n == 0: nothing was counted
     }
-    if (!dev && n) HIPC(e, hipMemcpyAsync(out, o, n, hipMemcpyDeviceToHost, s));
+    if (!dev && n && out) HIPC(e, hipMemcpyAsync(out, o, n, hipMemcpyDeviceToHost, s));
+    if (!dev && n && trace) HIPC(e, hipMemcpyAsync(rule_out, ro, n * 16, hipMemcpyDeviceToHost, s));
     // a host batch returns with its verdicts; a device batch is
     // stream-ordered (conn_last: its scratch is reused only behind it)
     if (sync || !dev) {

@@ -217,6 +217,7 @@ struct cls_engine {
     DevBuf s_rules, s_tctr, s_cctr;  // connection path: rule pool, table counter pointers, call counters
     DevBuf s_crows;                  // ... LDS counter rows of the workgroups
     DevBuf s_rule;                   // cls_classify_rules of host arrays: the rule per packet
+    DevBuf s_trace;                  // cls_connect_rules of host arrays: 4 rules per connection
     bool cctr_zero = false;          // s_cctr cleared since its allocation (the scatter launch keeps it zero)
     // counting connection batches' scatter events (Table::conn_ev), reused
     // once no table holds them: one record per batch, not one per table
@@ -305,9 +306,10 @@ void engine_close(cls_engine* e);
 int classify_locked(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n, uint8_t* verdict_out,
                     uint64_t* counters_out, uint32_t flags, void* stream);
 // sync = false: the batch's device work is only enqueued (the caller
-// synchronises `stream` before it returns)
+// synchronises `stream` before it returns); rule_out: the trace batch of
+// cls_connect_rules (out may then be null)
 int connect_locked(cls_engine* e, const cls_conn_soa* c, uint64_t n, uint8_t* out, uint32_t flags, void* stream,
-                   bool sync);
+                   bool sync, int32_t* rule_out = nullptr);
 int gen4_locked(cls_engine* e, const cls_traffic_spec* sp, uint64_t first, uint64_t n, uint32_t* src4,
                 uint32_t* dst4, uint16_t* sport, uint16_t* dport, uint8_t* proto, void* stream, bool sync);
 int gen16_locked(cls_engine* e, const cls_traffic_spec16* sp, uint64_t first, uint64_t n, uint8_t* src16,

@@ -585,6 +585,13 @@ __device__ __forceinline__ uint32_t conn_bm(const ConnArgs& a, const ConnDesc& D
 // non-nil ACL -> the call's counter space (descriptor ctr_off + rule), in LDS
 // (u32, folded into the u64 counters at the end) or with wave-aggregated
 // global atomics.
+// Tracing (cls_connect_rules, kCount 3): the same calls' terminating rules,
+// table-local (a job's rule as found, a counter-index word less its
+// descriptor's ctr_off, a slot word through slot_rule), -1 for a call not
+// made or on a nil ACL: one 16-B store per connection at rule_out + 4 i.  No
+// counters of any kind.  Its registers are the plain variants' plus the four
+// rules (profiles/r08a_conn_trace_regs.txt: 75-80 VGPRs, no scratch),
+// so it keeps their 6 waves per SIMD.
 // Workgroup size (launch_connect): the kernel holds ~80 VGPRs (6 waves per
 // SIMD), so 24 waves fit a CU -- three 512-thread workgroups where the LDS
 // allows, else two 768-thread ones where it allows those (the bench's
@@ -787,7 +794,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(kCount == 
                     uint32_t res, rule;
                     if (D.bm_off != 0xFFFFFFFFu) res = conn_bm<kLdsRules>(a, D, s1, d1, port, xp, rule);
                     else res = conn_scan<false, kLdsRules>(a, D, A(s1), A(d1), true, true, port, xp, rule);
-                    out = res | ((D.ctr_off + rule) << 2);
+                    out = res | ((kCount == 3 ? rule : D.ctr_off + rule) << 2);   // (the trace: the table's own index)
                 }
                 // the result over the entry's first word, then the owners read it
                 if (act) *(__attribute__((address_space(3))) uint32_t*)(jq + 8u * lane) = out;
@@ -827,7 +834,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(kCount == 
                         res = syn ? conn_scan<k16, kLdsRules>(a, D, xs, xd, x4s, x4d, xdp, xp, rule)
                                   : conn_scan<k16, kLdsRules>(a, D, xd, xs, x4d, x4s, xsp, xp, rule);
                     }
-                    out = res | ((D.ctr_off + rule) << 2);
+                    out = res | ((kCount == 3 ? rule : D.ctr_off + rule) << 2);   // (the trace: the table's own index)
                 }
                 // the owners take their results of this pass
 #pragma unroll
@@ -852,7 +859,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(kCount == 
 #pragma unroll
         for (int k = 0; k < 4; ++k) made[k] = (sm >> (2 + k)) & 1u;
         if (live) a.out[i] = uint8_t(v);
-        if constexpr (kCount != 0) {
+        if constexpr (kCount == 1 || kCount == 2) {
             uint32_t key[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -883,6 +890,22 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(kCount == 
 #pragma unroll
                 for (int k = 0; k < 4; ++k) wave_count(gctr, key[k]);
             }
+        }
+        if constexpr (kCount == 3) {
+            int32_t tr[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                tr[k] = -1;
+                if (made[k] && di[k] >= 0) {                    // not made, or a nil ACL: -1
+                    if (job[k]) {
+                        tr[k] = int32_t(rj[k] >> 2);
+                    } else {
+                        const ConnDesc D = conn_desc(a, uint32_t(di[k]));
+                        tr[k] = a.pre_rules ? int32_t((w[k] >> 2) - D.ctr_off) : int32_t(D.slot_rule[w[k] >> 2]);
+                    }
+                }
+            }
+            if (live) reinterpret_cast<int4*>(a.rule_out)[i] = make_int4(tr[0], tr[1], tr[2], tr[3]);
         }
     }
     if constexpr (kCount == 1) {
@@ -1173,6 +1196,8 @@ hipError_t launch_connect(const ConnArgs& a, bool k16, bool lds_rules, int count
     CONN_CASE(false, true, 0, false) CONN_CASE(false, true, 1, false) CONN_CASE(false, true, 2, false)
     CONN_CASE(true, false, 0, false) CONN_CASE(true, false, 1, false) CONN_CASE(true, false, 2, false)
     CONN_CASE(true, true, 0, false) CONN_CASE(true, true, 1, false) CONN_CASE(true, true, 2, false)
+    CONN_CASE(false, false, 3, true) CONN_CASE(false, true, 3, true) CONN_CASE(false, false, 3, false)
+    CONN_CASE(false, true, 3, false) CONN_CASE(true, false, 3, false) CONN_CASE(true, true, 3, false)
 #undef CONN_CASE
     return hipErrorInvalidValue;
 }

@@ -339,9 +339,12 @@ struct ConnArgs {
                                  // SYN-ACK result << 2, batches that do not count)
     uint32_t bm_steps;           // bitmap forms: lower-bound steps of the largest interval table
     uint32_t job_lds;            // IPv4: LDS byte offset of the waves' job lists (512 B per wave)
+    int32_t* rule_out;           // the trace variant (launch_connect count 3): 4 rules per
+                                 // connection, 16-B aligned (last: the other fields' offsets stay)
 };
 // k16: 16-byte addresses; lds_rules: stage the pool; count: 0 none, 1 LDS
-// counters, 2 global (wave-aggregated) counters; grid: persistent workgroups
+// counters, 2 global (wave-aggregated) counters, 3 no counters but the calls'
+// terminating rules to a.rule_out (cls_connect_rules); grid: persistent workgroups
 // of `block` threads (512, 768 or 1024); lds: dynamic LDS bytes (pool, LDS
 // counters, a.meta_lds tables)
 hipError_t launch_connect(const ConnArgs& a, bool k16, bool lds_rules, int count, int grid, int block, size_t lds,

@@ -454,6 +454,72 @@ class Engine:
         self._check(_abi.lib().cls_connect_batch(self.h, C.byref(cs), n, _ptr(out), flags | _abi.F_DEVICE, None))
         return out
 
+    def connect_rules(self, src_if, dst_if, src, dst, proto, sport, dport, mode: str = "auto", out=None,
+                      rules_out=None, stream=None):
+        """connect_batch with the trace (cls_connect_rules): the ConnectionAction
+        of every connection and the terminating rule of each of its four
+        evalACL calls, in testConnection's order (SYN src inbound, SYN dst
+        outbound, SYN-ACK dst inbound, SYN-ACK src outbound): the index in
+        that ACL's table, R for the default DENY, -1 for a call not made or on
+        a nil ACL.  The tables are the interfaces' bindings at the call
+        (if_acls).  No counters.  Host arrays: (verdict uint8[n], rules
+        int32[n, 4]).  Torch device tensors: the same as GPU tensors (``out``
+        uint8[n] / ``rules_out`` int32[n, 4], contiguous, when given),
+        enqueued on ``stream`` (default: the engine's)."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        fn = _abi.lib().cls_connect_rules
+        if _is_torch(src):
+            import torch
+            v16 = src.dim() == 2
+            arrs = (src_if, dst_if, src, dst, sport, dport, proto)
+            sizes = (4, 4, 1 if v16 else 4, 1 if v16 else 4, 2, 2, 1)
+            n = src.shape[0]
+            for x, sz in zip(arrs, sizes):
+                if not (_is_torch(x) and x.is_cuda and x.is_contiguous() and x.element_size() == sz and
+                        x.shape[0] == n):
+                    raise ClsError("device connection batch: contiguous GPU tensors of element sizes %s" % (sizes,))
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=src.device)
+            elif not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.element_size() == 1 and
+                      out.shape[0] == n):
+                raise ClsError("device connection batch: out must be a contiguous uint8 GPU tensor of n elements")
+            if rules_out is None:
+                rules_out = torch.empty((n, 4), dtype=torch.int32, device=src.device)
+            elif not (_is_torch(rules_out) and rules_out.is_cuda and rules_out.is_contiguous() and
+                      rules_out.dtype == torch.int32 and tuple(rules_out.shape) == (n, 4) and
+                      rules_out.data_ptr() % 16 == 0):
+                raise ClsError("device connection trace: rules_out must be a contiguous, 16-byte aligned int32 "
+                               "GPU tensor of shape (n, 4)")
+            s = None
+            if stream is not None:
+                s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+            if v16:
+                pk = _abi.PktSoa(_abi.AF_V16, None, None, _ptr(src), _ptr(dst), _ptr(sport), _ptr(dport), _ptr(proto))
+            else:
+                pk = _abi.PktSoa(_abi.AF_V4, _ptr(src), _ptr(dst), None, None, _ptr(sport), _ptr(dport), _ptr(proto))
+            cs = _abi.ConnSoa(pk, _ptr(src_if), _ptr(dst_if))
+            self._check(fn(self.h, C.byref(cs), n, _ptr(out), _ptr(rules_out), flags | _abi.F_DEVICE, s))
+            return out, rules_out
+        v16 = np.asarray(src).ndim == 2
+        if v16:
+            s = np.ascontiguousarray(src, np.uint8).reshape(-1, 16)
+            d = np.ascontiguousarray(dst, np.uint8).reshape(-1, 16)
+        else:
+            s, d = np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(dst, np.uint32)
+        si, di = np.ascontiguousarray(src_if, np.uint32), np.ascontiguousarray(dst_if, np.uint32)
+        p, sp = np.ascontiguousarray(proto, np.uint8), np.ascontiguousarray(sport, np.uint16)
+        dp = np.ascontiguousarray(dport, np.uint16)
+        n = len(s)
+        v = np.zeros(n, np.uint8)
+        r = np.full((max(n, 1), 4), -1, np.int32)[:n]       # (a valid pointer for n = 0)
+        if v16:
+            pk = _abi.PktSoa(_abi.AF_V16, None, None, _ptr(s), _ptr(d), _ptr(sp), _ptr(dp), _ptr(p))
+        else:
+            pk = _abi.PktSoa(_abi.AF_V4, _ptr(s), _ptr(d), None, None, _ptr(sp), _ptr(dp), _ptr(p))
+        cs = _abi.ConnSoa(pk, _ptr(si), _ptr(di))
+        self._check(fn(self.h, C.byref(cs), n, _ptr(v), _ptr(r), flags, None))
+        return v, r
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -736,12 +802,24 @@ class ACLEngine:
     def connection_batch(self, calls, count: bool = False):
         """calls: list of (fn name, args).  One GPU launch for all of them: the
         IPv4 layout when every endpoint is IPv4, else the 16-byte layout."""
-        out = [None] * len(calls)
+        return self._connections(calls, count, False)
+
+    def connection_trace(self, calls):
+        """connection_batch with the matched rules the reference logs
+        (aclengine_mock.go:651-654): per call (ConnectionAction, [(ACL name,
+        rule index or None for the default DENY) of every evalACL call
+        testConnection made on a non-nil ACL, in its order]) -- a call that
+        fails before testConnection has an empty list.  One GPU launch
+        (Engine.connect_rules); no counters."""
+        return self._connections(calls, False, True)
+
+    def _connections(self, calls, count: bool, trace: bool):
+        # (a call the reference fails before testConnection stays a Failure)
+        out = [(CONN_FAILURE, []) if trace else CONN_FAILURE for _ in calls]
         rows = []
         for i, (fn, args) in enumerate(calls):
             r = self.resolve(fn, args)
             if r == CONN_FAILURE:
-                out[i] = CONN_FAILURE
                 continue
             sif, sip, dif, dip, proto, sport, dport = r
             rows.append((i, self.engine.if_id(sif), self.engine.if_id(dif), sip, dip, proto, sport, dport))
@@ -758,6 +836,25 @@ class ACLEngine:
                 raise ClsError("connection endpoint is not an IPv4 or IPv6 address")
             src = np.frombuffer(b"".join(a for a, _ in a16), np.uint8).reshape(-1, 16)
             dst = np.frombuffer(b"".join(b for _, b in a16), np.uint8).reshape(-1, 16)
+        if trace:
+            res, rules = self.engine.connect_rules(meta[:, 0], meta[:, 1], src, dst, meta[:, 2], meta[:, 3],
+                                                   meta[:, 4])
+            names = {}                              # table id -> (ACL name, R)
+
+            def acl(tid):
+                if tid not in names:
+                    a = self._acl_of_table(tid)
+                    names[tid] = (a.acl_name, len(a.rules))
+                return names[tid]
+            for (i, s_id, d_id, *_), v, row in zip(rows, res, rules):
+                (s_in, s_out), (d_in, d_out) = self.engine.if_acls(s_id), self.engine.if_acls(d_id)
+                made = []
+                for tid, rule in zip((s_in, d_out, d_in, s_out), row):
+                    if rule >= 0:
+                        name, n_rules = acl(tid)
+                        made.append((name, int(rule) if rule < n_rules else None))
+                out[i] = (int(v), made)
+            return out
         res = self.engine.connect_batch(meta[:, 0], meta[:, 1], src, dst, meta[:, 2], meta[:, 3], meta[:, 4],
                                         count=count)
         for (i, *_), v in zip(rows, res):
