@@ -1,4 +1,4 @@
-"""CPU: the bitmap form of connection-path ACLs (engine.cpp conn_bitmap4).
+"""CPU: the bitmap form of connection-path ACLs (connect.cpp conn_bitmap4).
 
 cls_connect_batch evaluates linear IPv4 ACLs through per-ACL interval tables
 (source, destination, each protocol's destination port) with one rule bit

@@ -171,7 +171,7 @@ def test_connections_at_scale_match_oracle(seed, mode):
 @pytest.mark.parametrize("bitmap", ["1", "0"])
 def test_connections_bitmap_form_match_oracle(bitmap, no_lds):
     """Device batches with the default selection: the linear IPv4 ACLs (1-300
-    random rules) in the bitmap form (engine.cpp conn_bitmap4) or scanned
+    random rules) in the bitmap form (connect.cpp conn_bitmap4) or scanned
     (option conn_bitmap=0), the pool in LDS or (no_lds 1) global memory,
     the counters and tables in global memory (no_lds 6); verdicts and per-(ACL, rule) counters against orc_test_connection."""
     from vpp_amd.engine import Engine
@@ -276,7 +276,7 @@ def test_global_tables_match_oracle(fam, count):
 @pytest.mark.parametrize("count", [False, True])
 def test_device_plan_follows_binding_changes(count):
     """A device batch keeps its plan (descriptors, interface table, rule pool)
-    until a table or binding changes (engine.cpp ConnPlan / conn_gen): after
+    until a table or binding changes (connect.cpp conn_plan_build, ConnPlan / conn_gen): after
     a replaced ACL, a deleted one, a re-put of equal rules on other
     interfaces (the rebind path) and a new interface, the same device batch
     must follow the new bindings -- verdicts and counters against the

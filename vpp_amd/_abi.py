@@ -15,8 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CONTIVCLS_LIB: diagnostics only (A/B timing of kernel build variants)
 LIB_PATH = os.environ.get("CONTIVCLS_LIB") or os.path.join(_HERE, "libcontivcls.so")
 
-SOURCES = ("kernels.hip", "kernels_dev.hpp", "k4_ldsv.hip", "k4_rest.hip", "k4_pair.hip", "k16.hip", "kernels.hpp", "compile.cpp",
-           "compile.hpp", "engine.cpp", "goparse.hpp", "engine_int.hpp", "fleet.cpp", "options.cpp", "options.hpp")
+# every native source, by listing: a new unit is hashed without being named here
+SOURCES = tuple(sorted(f for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".hip", ".hpp", ".cpp"))))
 
 
 def source_hash() -> str:

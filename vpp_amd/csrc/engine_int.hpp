@@ -1,5 +1,6 @@
-// Internal types of the engine (engine.cpp, fleet.cpp): device buffers,
-// compiled tables with their device copies, the per-device engine state.
+// Internal types of the engine (engine.cpp, connect.cpp, fleet.cpp): device
+// buffers, compiled tables with their device copies, the per-device engine
+// state.
 // Not part of the C ABI (include/contivcls.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -192,6 +193,7 @@ struct ConnPlan {
     std::vector<uint8_t> pool;
     uint32_t n_ctr = 0;
     uint32_t bm_steps = 0;                                // lower-bound steps of the largest bitmap table
+    std::vector<uint8_t> launch;                          // scratch of a batch's large-ACL pass (one per big)
 };
 
 struct cls_engine {
@@ -300,7 +302,24 @@ inline int fail(cls_engine* e, int code, const char* fmt, ...) {
                         __FILE__, __LINE__);                                             \
     } while (0)
 
-// ---- engine.cpp internals used by fleet.cpp (the caller holds e->mu) -----
+constexpr uint64_t kClsChunk = 1ull << 30;   // packets per classify launch (32-bit offsets)
+
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// ---- engine.cpp internals used by connect.cpp ----------------------------
+Cls4Dev cls4_dev(const Cls4Image& im, const DevBuf& d_img, const DevBuf& d_lin, uint32_t n_lin, uint32_t n_rules);
+// The v4 classifier of a table (its kernel never reads the linear rules:
+// every protocol has a cell).
+inline Cls4Dev table_dev(const Table& t) { return cls4_dev(t.img, t.d_img, DevBuf(), 0, t.n_rules); }
+// Packets in an image's frame: src and dst exchanged for a destination-keyed one.
+inline Pkts4 framed(const Cls4Image& im, const Pkts4& p) {
+    return im.swap ? Pkts4{p.dst, p.src, p.dport, p.proto, p.n} : p;
+}
+Fe16 fe16(const Cls16Image& m, const DevBuf& d_src_search);
+int cls_grid(const cls_engine* e, bool use_cls, bool lds_resident, uint32_t lds_bytes, uint64_t n);
+int upload(cls_engine* e, DevBuf& d, const Cls4Image& im);
+
+// ---- engine.cpp / connect.cpp internals used by fleet.cpp (the caller holds e->mu)
 int engine_open(int device, cls_engine** out);
 void engine_close(cls_engine* e);
 int classify_locked(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n, uint8_t* verdict_out,

@@ -34,7 +34,7 @@ struct Opts {
     int wg_per_cu = 0;          // classify workgroups per CU (0: by LDS)
     bool debug_floor = false;   // stderr: every stream shape's time
     bool fold_split = true;     // finish launch: a slot tile's rows over several blocks when tiles are few
-    // ---- connection batches (engine.cpp) ----------------------------------
+    // ---- connection batches (connect.cpp) ---------------------------------
     bool conn_bitmap = true;    // bitmap form of linear IPv4 ACLs
     bool conn_pair = true;      // both tuples of a large ACL in one launch (classify4_pair)
     bool conn_pair16 = true;    // ... of a 16-byte batch too, on the table's pair image (classify16_pair)
