@@ -608,6 +608,124 @@ func (en *Engine) one(c Conn) aclengine.ConnectionAction {
 	return res[0]
 }
 
+// Probe is one (protocol, source port, destination port) question of a
+// reachability matrix.
+type Probe struct {
+	Protocol aclengine.ProtocolType
+	SrcPort  uint16
+	DstPort  uint16
+}
+
+// Reach is the result of ReachMatrix over P probes and N pods: Verdicts[(p*N +
+// s)*N + d] is what ConnectionPodToPod(pods[s], pods[d], probes[p]...)
+// returns, Hist[p][a] the cells of probe p with ConnectionAction a, Allow[p*N
+// + s] the pods that pods[s] reaches on probe p (ConnActionAllow).
+type Reach struct {
+	N, P     int
+	Verdicts []aclengine.ConnectionAction
+	Hist     [][4]uint64
+	Allow    []uint32
+}
+
+// ReachMatrix answers what the reference's tests ask by looping
+// ConnectionPodToPod over pods and ports (aclengine_mock.go:243-300) -- who
+// reaches whom, on which probe -- in one engine call (cls_reach_matrix): the
+// engine receives the pods' endpoints and the probes, never a row per cell.
+// Pods that ConnectionPodToPod fails before testConnection (unregistered, no
+// interface) stay out of the call: their rows and columns are
+// ConnActionFailure.  The IPv4 layout when every endpoint is IPv4, else the
+// 16-byte layout.  count: add every evalACL call's terminating rule to the
+// tables' connection counters (ConnCounters): the rules left at zero are
+// those no pod pair can hit.
+func (en *Engine) ReachMatrix(pods []podmodel.ID, probes []Probe, count bool) (*Reach, error) {
+	en.Lock()
+	defer en.Unlock()
+	N, P := len(pods), len(probes)
+	out := &Reach{N: N, P: P, Verdicts: make([]aclengine.ConnectionAction, P*N*N), Hist: make([][4]uint64, P),
+		Allow: make([]uint32, P*N)}
+	for i := range out.Verdicts {
+		out.Verdicts[i] = aclengine.ConnActionFailure
+	}
+	for p := range out.Hist {
+		out.Hist[p][aclengine.ConnActionFailure] = uint64(N) * uint64(N)
+	}
+	var strs cstrs
+	defer strs.free()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil {
+			continue
+		}
+		ifName, ok := en.podIf(pod, cfg)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	if n == 0 || P == 0 {
+		return out, nil
+	}
+	proto, sport, dport := make([]uint8, P), make([]uint16, P), make([]uint16, P)
+	for p, q := range probes {
+		proto[p], sport[p], dport[p] = uint8(q.Protocol), q.SrcPort, q.DstPort
+	}
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds cls_reach_spec on the C stack
+	res, hist, allow := make([]uint8, P*n*n), make([]uint64, 4*P), make([]uint32, P*n)
+	flags := C.uint32_t(0)
+	if count {
+		flags |= C.CLS_F_COUNT
+	}
+	var rc C.int
+	if v4 {
+		a4 := make([]uint32, n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To4()
+			a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+		}
+		rc = C.clsg_reach_matrix_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+			(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+			(*C.uint8_t)(&res[0]), (*C.uint64_t)(&hist[0]), (*C.uint32_t)(&allow[0]), flags)
+	} else {
+		a16 := make([]byte, 16*n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To16()
+			if a == nil {
+				return nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+			}
+			copy(a16[16*k:], a)
+		}
+		rc = C.clsg_reach_matrix_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+			(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+			(*C.uint8_t)(&res[0]), (*C.uint64_t)(&hist[0]), (*C.uint32_t)(&allow[0]), flags)
+	}
+	if rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	for p := 0; p < P; p++ {
+		for a := 0; a < 4; a++ {
+			out.Hist[p][a] = hist[4*p+a]
+		}
+		// the pods left out: N*N - n*n more failures
+		out.Hist[p][aclengine.ConnActionFailure] += uint64(N)*uint64(N) - uint64(n)*uint64(n)
+		for s := 0; s < n; s++ {
+			out.Allow[p*N+at[s]] = allow[p*n+s]
+			for d := 0; d < n; d++ {
+				out.Verdicts[(p*N+at[s])*N+at[d]] = aclengine.ConnectionAction(res[(p*n+s)*n+d])
+			}
+		}
+	}
+	return out, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

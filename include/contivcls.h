@@ -188,8 +188,9 @@ int cls_abi_version(void);
  * plans (other_cap, wg_per_cu, conn_bitmap, conn_pair, conn_pair16, conn_pre_rules,
  * conn_pre_narrow, pair_qcap, pair_lq, pair_other_global, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
- * debug_modes, debug_conn, debug_floor) for later calls; every one keeps
- * verdicts and counters exact.  The library never reads the environment:
+ * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
+ * up to a multiple of 1024 --, debug_modes, debug_conn, debug_floor) for
+ * later calls; every one keeps verdicts and counters exact.  The library never reads the environment:
  * an engine runs its defaults unless told otherwise here.  CLS_E_INVAL for
  * an unknown key or a malformed value. */
 int cls_engine_set_option(cls_engine* e, const char* key, const char* value);
@@ -374,6 +375,49 @@ int cls_connect_rules(cls_engine* e, const cls_conn_soa* conns, uint64_t n,
  * reset (reset != 0 clears them after the read).  Waits for pending device
  * work.  The reference has no counters. */
 int cls_conn_counters(cls_engine* e, uint32_t table_id, uint64_t* counters_out, uint32_t reset);
+
+/* ---- reachability matrix (ConnectionPodToPod looped over pods and ports,
+ * aclengine_mock.go:243-300) ----------------------------------------------
+ * Who reaches whom, on which probe: testConnection over every (probe,
+ * source, destination) cell of N endpoints x P probes in one call, evaluated
+ * on the device from the endpoint and probe lists -- the P x N x N rows a
+ * connection batch would need are never built by the caller.  Cell (p, s, d),
+ * at index (p N + s) N + d, is exactly testConnection(if_id[s], addr[s],
+ * if_id[d], addr[d], proto[p], sport[p], dport[p]); the diagonal and the
+ * pairs that share an interface are included (the same-interface REFLECT
+ * short-cuts, :412-421, apply as in a batch).  The bindings are snapshotted
+ * once for the whole call.  The arrays of `spec` are host memory, copied
+ * before the call returns.  Outputs, each optional (not all three NULL):
+ *   verdict_out [P][N][N]  ConnectionAction per cell (NULL: CLS_F_NO_VERDICT)
+ *   hist_out    [P][4]     cells per ConnectionAction
+ *   allow_out   [P][N]     per (probe, source) the destinations with CLS_CONN_ALLOW
+ * hist_out and allow_out are overwritten, not accumulated.  Flags:
+ * CLS_F_DEVICE -- the outputs are device memory on the engine's GPU
+ * (verdict_out 16-byte, hist_out 8-byte, allow_out 4-byte aligned) and the
+ * call only enqueues on `stream`, ordered like a device connection batch;
+ * without it they are host arrays and the call returns with the results.
+ * CLS_F_NO_VERDICT: verdict_out may be NULL.  CLS_F_COUNT, CLS_F_CONN_CLS,
+ * CLS_F_FORCE_LINEAR: as cls_connect_batch (with CLS_F_COUNT the connection
+ * counters afterwards show which rules no endpoint pair can hit).  The
+ * matrix is evaluated in tiles of at most `reach_tile` connections
+ * (cls_engine_set_option), each a device connection batch over engine-owned
+ * scratch.  CLS_E_INVAL, before any device work: N or P zero, a bad af, a
+ * NULL array, no output, verdict_out NULL without CLS_F_NO_VERDICT, a
+ * misaligned device output, an unknown interface id, P N^2 > 2^36.  On a
+ * multi-device engine the call runs on the first device. */
+typedef struct cls_reach_spec {
+    uint32_t af;                 /* CLS_AF_V4: addr4; CLS_AF_V16: addr16 (IPv4-mapped = IPv4) */
+    uint32_t n_endpoints;        /* N >= 1 */
+    const uint32_t* if_id;       /* N interface ids (cls_if_id) */
+    const uint32_t* addr4;       /* N host-order IPv4 */
+    const uint8_t* addr16;       /* N x 16 network-order bytes */
+    uint32_t n_probes;           /* P >= 1 */
+    const uint8_t* proto;        /* P ProtocolType */
+    const uint16_t* sport;       /* P */
+    const uint16_t* dport;       /* P */
+} cls_reach_spec;
+int cls_reach_matrix(cls_engine* e, const cls_reach_spec* spec, uint8_t* verdict_out,
+                     uint64_t* hist_out, uint32_t* allow_out, uint32_t flags, void* stream);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

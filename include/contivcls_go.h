@@ -153,6 +153,47 @@ static inline int clsg_connect_rules_v16(cls_engine* e, const uint32_t* src_if, 
     return cls_connect_rules(e, &c, n, out, rules, flags, NULL);
 }
 
+/* cls_reach_matrix over IPv4 endpoints: testConnection for every (probe,
+ * source, destination) cell of n endpoints x n_probes probes -- what the
+ * reference answers by looping ConnectionPodToPod over pods and ports
+ * (aclengine_mock.go:243-300).  Host outputs; verdict (n_probes x n x n),
+ * hist (n_probes x 4) and allow (n_probes x n) may each be NULL (not all;
+ * verdict NULL needs CLS_F_NO_VERDICT). */
+static inline int clsg_reach_matrix_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                       const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                       uint32_t n_probes, uint8_t* verdict, uint64_t* hist, uint32_t* allow,
+                                       uint32_t flags) {
+    cls_reach_spec r;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    return cls_reach_matrix(e, &r, verdict, hist, allow, flags, NULL);
+}
+
+/* cls_reach_matrix over 16-byte endpoints (n x 16 network-order bytes). */
+static inline int clsg_reach_matrix_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                        const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                        uint32_t n_probes, uint8_t* verdict, uint64_t* hist, uint32_t* allow,
+                                        uint32_t flags) {
+    cls_reach_spec r;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    return cls_reach_matrix(e, &r, verdict, hist, allow, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -55,7 +55,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_batch_destroy", "cls_batch_shards", "cls_batch_shard", "cls_batch_field", "cls_batch_mirror",
            "cls_batch_upload", "cls_batch_download", "cls_batch_gen_traffic_v4", "cls_batch_gen_traffic_v16",
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
-           "cls_comm_init", "cls_comm_info"]
+           "cls_comm_init", "cls_comm_info", "cls_reach_matrix"]
 
 
 class ClsRule(C.Structure):
@@ -77,6 +77,13 @@ class PktSoa(C.Structure):
 
 class ConnSoa(C.Structure):
     _fields_ = [("pkt", PktSoa), ("src_if", C.c_void_p), ("dst_if", C.c_void_p)]
+
+
+class ReachSpec(C.Structure):
+    """cls_reach_spec: N endpoints (interface id, address) x P probes."""
+    _fields_ = [("af", C.c_uint32), ("n_endpoints", C.c_uint32), ("if_id", C.c_void_p), ("addr4", C.c_void_p),
+                ("addr16", C.c_void_p), ("n_probes", C.c_uint32), ("proto", C.c_void_p), ("sport", C.c_void_p),
+                ("dport", C.c_void_p)]
 
 
 class Config(C.Structure):
@@ -204,6 +211,7 @@ def bind(path: str, strict: bool = True):
         "cls_connect_batch": (C.c_int, [vp, C.POINTER(ConnSoa), u64, vp, u32, vp]),
         "cls_connect_rules": (C.c_int, [vp, C.POINTER(ConnSoa), u64, vp, vp, u32, vp]),
         "cls_conn_counters": (C.c_int, [vp, u32, vp, u32]),
+        "cls_reach_matrix": (C.c_int, [vp, C.POINTER(ReachSpec), vp, vp, vp, u32, vp]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -231,6 +231,13 @@ struct cls_engine {
     // connection batch over unchanged bindings uploads nothing
     std::vector<uint8_t> up_desc, up_ifs, up_rules, up_tctr;
     DevBuf s_pool;
+    // cls_reach_matrix (reach.cpp): the call's endpoint and probe tables (one
+    // blob, reach_up its host copy: the source of an unsynchronised upload
+    // outlives the call), a tile's connection arrays and verdict bytes, the
+    // u64 histogram and u32 allow-count accumulators.  Shared with no other
+    // call; reused and grown like the connection scratch (conn_last)
+    DevBuf r_tab, r_src, r_dst, r_sif, r_dif, r_sport, r_dport, r_proto, r_verdict, r_hist, r_allow;
+    std::vector<uint8_t> reach_up;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

@@ -369,6 +369,44 @@ hipError_t launch_conn_scatter(const ConnDesc* desc, unsigned long long* const* 
                                uint32_t max_rules, unsigned long long* call_ctr, uint32_t n_slabs, bool clear,
                                uint32_t n_ctr, hipStream_t s);
 
+// ---- the reachability matrix (k_reach.hip; contivcls.h cls_reach_matrix) --
+// One tile of the matrix: connections [0, n) of the tile are the cells from
+// (p0, s0, d0) on in (probe, source, destination) order, the destination
+// varying fastest, over N endpoints.  Every index the kernels form is 32-bit:
+// n <= 2^30, N <= 2^18, and the host passes the outputs offset to the tile's
+// first probe and row.
+struct ReachTile {
+    uint32_t n_ep;               // N
+    uint32_t p0, s0, d0;         // the tile's first cell
+    uint32_t n;                  // connections in the tile (none past the matrix's end)
+};
+// The tile's connections written as a device batch's arrays (cls_conn_soa):
+// four consecutive connections per lane -- 16-B stores to src / dst (one per
+// address with 16-byte addresses) / src_if / dst_if, 8-B to the ports, 4-B to
+// the protocols; the arrays hold whole groups of four (the connections past n
+// of the last group repeat the last one).  ep_if: N interface ids; ep_addr:
+// N u32 or N 16-B addresses; probe: P x {sport | dport << 16, proto}.
+struct ReachExpand {
+    const uint32_t* ep_if;
+    const void* ep_addr;
+    const uint2* probe;
+    uint32_t *src_if, *dst_if;
+    void *src, *dst;
+    uint16_t *sport, *dport;
+    uint8_t* proto;
+};
+hipError_t launch_reach_expand(const ReachTile& t, const ReachExpand& x, bool k16, int n_cu, hipStream_t s);
+// The tile's ConnectionActions summed: hist[4 p' + action] += connections
+// (hist at the tile's first probe, or null), allow[r'] += the row's
+// CLS_CONN_ALLOW cells (allow at the tile's first (probe, source) row, or
+// null).  verdict: the tile's n bytes, 4-B aligned.  A workgroup histograms
+// kReachChunk connections at a time in LDS (the chunk's first kReachLdsProbes
+// probes; later ones straight to global memory) and adds each non-zero bin
+// once; a wave whose 256 connections lie in one row adds its count once.
+constexpr uint32_t kReachBlock = 1024, kReachChunk = 4 * kReachBlock, kReachLdsProbes = 64;
+hipError_t launch_reach_reduce(const ReachTile& t, const uint8_t* verdict, unsigned long long* hist,
+                               uint32_t* allow, int n_cu, hipStream_t s);
+
 struct TrafficDev {
     uint64_t seed;
     uint32_t pct_pod, pct_dst, pct_port, pct_icmp;

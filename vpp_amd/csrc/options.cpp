@@ -88,6 +88,15 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
         o.pair_qcap_set = !reset;
         return true;
     }
+    if (k == "reach_tile") {
+        // a tile is one connect_locked batch (at most 2^30 connections)
+        if (!reset && (x < 256 || x > (1ll << 30))) {
+            why = "option reach_tile: 256 .. 2^30 connections";
+            return false;
+        }
+        o.reach_tile = reset ? d.reach_tile : uint32_t((x + 1023) & ~1023ll);
+        return true;
+    }
     if (k == "orient") {
         const std::string v = reset ? "" : value;
         if (!reset && v != "src" && v != "dst") {

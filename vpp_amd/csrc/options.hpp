@@ -56,6 +56,9 @@ struct Opts {
     int conn_plan = -1;         // counting LDS plan 0..3 = 32j 16j 32s 16s (-1: scored)
     bool conn_flush_atomic = false;  // LDS counters flushed by device atomics, not per-workgroup rows
     bool debug_conn = false;    // stderr: a connection launch's LDS plan
+    // ---- reachability matrix (reach.cpp) ----------------------------------
+    uint32_t reach_tile = 16u << 20; // connections per tile (>= 256, rounded up to a multiple of 1024; 16 Mi
+                                     // measured best of 1 / 4 / 16 Mi, profiles/reach_ab_af{4,16}.txt)
     // ---- batches (fleet.cpp) ----------------------------------------------
     int batch_layout = 2;       // 0 packed, 1 one allocation per field, 2 staggered fields
 };

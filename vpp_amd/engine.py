@@ -520,6 +520,65 @@ class Engine:
         self._check(fn(self.h, C.byref(cs), n, _ptr(v), _ptr(r), flags, None))
         return v, r
 
+    def reach_matrix(self, if_ids, addrs, protos, sports, dports, mode: str = "auto", count: bool = False,
+                     verdicts: bool = True, hist: bool = True, allow: bool = True, out=None, stream=None):
+        """The reachability matrix (cls_reach_matrix): testConnection over every
+        (probe, source, destination) cell of N endpoints -- ``if_ids`` (N,)
+        and ``addrs`` (N,) host-order u32 or (N, 16) network-order bytes -- and
+        P probes (``protos``, ``sports``, ``dports``), evaluated on the device
+        from these lists alone.  Returns (verdicts [P, N, N] u8 | None, hist
+        [P, 4] u64 | None: cells per ConnectionAction, allow [P, N] u32 | None:
+        per (probe, source) the destinations it reaches); ``verdicts`` /
+        ``hist`` / ``allow`` False leaves one out (not all three).  mode and
+        count: as connect_batch.  The inputs are always host arrays.  out:
+        None for numpy results (the call returns with them), or a sequence
+        (verdicts, hist, allow) of contiguous torch GPU tensors -- u8
+        [P, N, N], 8-byte [P, 4], 4-byte [P, N]; None for a wanted one
+        allocates it -- which selects the device form: the call only enqueues
+        on ``stream`` (default: the engine's) and returns the tensors."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        if count:
+            flags |= _abi.F_COUNT
+        if not verdicts:
+            flags |= _abi.F_NO_VERDICT
+        ids = np.ascontiguousarray(if_ids, np.uint32)
+        a = np.asarray(addrs)
+        v16 = a.ndim == 2
+        a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+        pr, sp = np.ascontiguousarray(protos, np.uint8), np.ascontiguousarray(sports, np.uint16)
+        dp = np.ascontiguousarray(dports, np.uint16)
+        n, p = len(ids), len(pr)
+        if len(a) != n or len(sp) != p or len(dp) != p:
+            raise ClsError("reach matrix: N interface ids and addresses, P protocols and ports")
+        spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                              _ptr(a) if v16 else None, p, _ptr(pr), _ptr(sp), _ptr(dp))
+        want = (verdicts, hist, allow)
+        shapes = ((p, n, n), (p, 4), (p, n))
+        if out is None:
+            res = [np.zeros(sh, dt) if w else None for w, sh, dt in zip(want, shapes, (np.uint8, np.uint64, np.uint32))]
+            s = None
+        else:
+            import torch
+            flags |= _abi.F_DEVICE
+            res = list(out)
+            if len(res) != 3:
+                raise ClsError("reach matrix: out is (verdicts, hist, allow)")
+            for k, (w, sh, dt, sz) in enumerate(zip(want, shapes, (torch.uint8, torch.int64, torch.int32), (1, 8, 4))):
+                if not w:
+                    res[k] = None
+                elif res[k] is None:
+                    res[k] = torch.empty(sh, dtype=dt, device="cuda")
+                elif not (_is_torch(res[k]) and res[k].is_cuda and res[k].is_contiguous() and
+                          res[k].element_size() == sz and tuple(res[k].shape) == sh):
+                    raise ClsError("reach matrix: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                                   "elements" % (k, sh, sz))
+            s = None
+            if stream is not None:
+                s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        self._check(_abi.lib().cls_reach_matrix(self.h, C.byref(spec), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+                                                flags, s))
+        return tuple(res)
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -859,6 +918,40 @@ class ACLEngine:
                                         count=count)
         for (i, *_), v in zip(rows, res):
             out[i] = int(v)
+        return out
+
+    def connection_matrix(self, pods, probes, count: bool = False) -> np.ndarray:
+        """Who reaches whom: a [len(probes), len(pods), len(pods)] uint8 array
+        whose cell (p, s, d) equals connection_pod_to_pod(pods[s], pods[d],
+        *probes[p]) (ConnectionPodToPod, :243-300), probes being (proto,
+        sport, dport) triples -- one engine call (Engine.reach_matrix) over
+        the pods' endpoints instead of a row per cell.  Pods the reference
+        fails before testConnection (unregistered, no interface, no node
+        output interface) stay out of the engine call: their rows and columns
+        are CONN_FAILURE.  The IPv4 layout when every endpoint is IPv4, else
+        the 16-byte layout.  count: as connection_batch."""
+        out = np.full((len(probes), len(pods), len(pods)), CONN_FAILURE, np.uint8)
+        eps = []                                    # (index in pods, interface id, net.IP)
+        for i, pod in enumerate(pods):
+            cfg = self.pods.get(pod)
+            ifn = self._pod_if(pod, cfg) if cfg is not None else None
+            if ifn is not None:
+                eps.append((i, self.engine.if_id(ifn), cfg[0]))
+        if not eps or not probes:
+            return out
+        four = [_ip4(ip) for _, _, ip in eps]
+        if all(a is not None for a in four):
+            addrs = np.array(four, np.uint32)
+        else:
+            a16 = [_ip16(ip) for _, _, ip in eps]
+            if any(a is None for a in a16):
+                raise ClsError("connection endpoint is not an IPv4 or IPv6 address")
+            addrs = np.frombuffer(b"".join(a16), np.uint8).reshape(-1, 16)
+        pr = np.array(probes, np.int64).reshape(-1, 3)
+        v, _, _ = self.engine.reach_matrix([e[1] for e in eps], addrs, pr[:, 0], pr[:, 1], pr[:, 2], count=count,
+                                           hist=False, allow=False)
+        at = np.array([e[0] for e in eps])
+        out[:, at[:, None], at[None, :]] = v
         return out
 
     def connection_pod_to_pod(self, src_pod, dst_pod, proto, sport, dport):
