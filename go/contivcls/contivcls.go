@@ -726,6 +726,156 @@ func (en *Engine) ReachMatrix(pods []podmodel.ID, probes []Probe, count bool) (*
 	return out, nil
 }
 
+// ReachChange is one changed cell of ReachDiff: the probe's index, the source
+// and destination pods' indices, the baseline's byte and the new action.
+type ReachChange struct {
+	Probe, Src, Dst int
+	Was, Now        aclengine.ConnectionAction
+}
+
+// ReachDiff answers "what connectivity did this commit change?": the matrix
+// ReachMatrix(pods, probes) would return now, and the cells in which it
+// differs from base -- the Verdicts of an earlier ReachMatrix over the same
+// pods and probes -- in cell order, compared on the device in the same engine
+// call (cls_reach_diff): only the changed cells' records come back besides
+// the matrix.  The engine sees base restricted to the pods that reach
+// testConnection; the rows and columns of the others are compared here
+// against ConnActionFailure.
+func (en *Engine) ReachDiff(pods []podmodel.ID, probes []Probe, base []aclengine.ConnectionAction,
+	count bool) (*Reach, []ReachChange, error) {
+	en.Lock()
+	defer en.Unlock()
+	N, P := len(pods), len(probes)
+	if len(base) != P*N*N {
+		return nil, nil, errors.New("ReachDiff: base must hold P*N*N verdicts")
+	}
+	out := &Reach{N: N, P: P, Verdicts: make([]aclengine.ConnectionAction, P*N*N), Hist: make([][4]uint64, P),
+		Allow: make([]uint32, P*N)}
+	for i := range out.Verdicts {
+		out.Verdicts[i] = aclengine.ConnActionFailure
+	}
+	for p := range out.Hist {
+		out.Hist[p][aclengine.ConnActionFailure] = uint64(N) * uint64(N)
+	}
+	var strs cstrs
+	defer strs.free()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	inside := make([]bool, N)
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil {
+			continue
+		}
+		ifName, ok := en.podIf(pod, cfg)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		inside[i] = true
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	var inner []ReachChange // the engine's records, over pods
+	if n > 0 && P > 0 {
+		proto, sport, dport := make([]uint8, P), make([]uint16, P), make([]uint16, P)
+		for p, q := range probes {
+			proto[p], sport[p], dport[p] = uint8(q.Protocol), q.SrcPort, q.DstPort
+		}
+		// every slice goes to the shim as its own pointer (pointer-free Go
+		// memory); the shim builds both structs on the C stack
+		sub := make([]uint8, P*n*n)
+		for p := 0; p < P; p++ {
+			for s := 0; s < n; s++ {
+				for d := 0; d < n; d++ {
+					sub[(p*n+s)*n+d] = uint8(base[(p*N+at[s])*N+at[d]])
+				}
+			}
+		}
+		res, hist, allow := make([]uint8, P*n*n), make([]uint64, 4*P), make([]uint32, P*n)
+		rec := make([]uint32, 4*P*n*n) // 16-byte records: probe, src, dst, was | now << 8
+		var total C.uint64_t
+		flags := C.uint32_t(0)
+		if count {
+			flags |= C.CLS_F_COUNT
+		}
+		var rc C.int
+		if v4 {
+			a4 := make([]uint32, n)
+			for k := 0; k < n; k++ {
+				a := ips[k].To4()
+				a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+			}
+			rc = C.clsg_reach_diff_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+				(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+				(*C.uint8_t)(&sub[0]), (*C.uint8_t)(&res[0]), (*C.uint64_t)(&hist[0]), (*C.uint32_t)(&allow[0]),
+				unsafe.Pointer(&rec[0]), C.uint64_t(P*n*n), &total, nil, nil, flags)
+		} else {
+			a16 := make([]byte, 16*n)
+			for k := 0; k < n; k++ {
+				a := ips[k].To16()
+				if a == nil {
+					return nil, nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+				}
+				copy(a16[16*k:], a)
+			}
+			rc = C.clsg_reach_diff_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+				(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+				(*C.uint8_t)(&sub[0]), (*C.uint8_t)(&res[0]), (*C.uint64_t)(&hist[0]), (*C.uint32_t)(&allow[0]),
+				unsafe.Pointer(&rec[0]), C.uint64_t(P*n*n), &total, nil, nil, flags)
+		}
+		if rc != C.CLS_OK {
+			return nil, nil, en.lastErr()
+		}
+		for p := 0; p < P; p++ {
+			for a := 0; a < 4; a++ {
+				out.Hist[p][a] = hist[4*p+a]
+			}
+			// the pods left out: N*N - n*n more failures
+			out.Hist[p][aclengine.ConnActionFailure] += uint64(N)*uint64(N) - uint64(n)*uint64(n)
+			for s := 0; s < n; s++ {
+				out.Allow[p*N+at[s]] = allow[p*n+s]
+				for d := 0; d < n; d++ {
+					out.Verdicts[(p*N+at[s])*N+at[d]] = aclengine.ConnectionAction(res[(p*n+s)*n+d])
+				}
+			}
+		}
+		for k := 0; k < int(total); k++ {
+			r := rec[4*k : 4*k+4]
+			inner = append(inner, ReachChange{Probe: int(r[0]), Src: at[r[1]], Dst: at[r[2]],
+				Was: aclengine.ConnectionAction(r[3] & 0xFF), Now: aclengine.ConnectionAction(r[3] >> 8 & 0xFF)})
+		}
+	}
+	if n == N {
+		return out, inner, nil
+	}
+	// merge, in cell order, with the cells of the pods left out that the
+	// baseline did not already hold as failures (at is ascending, so the
+	// engine's records are in cell order over pods too)
+	var changes []ReachChange
+	k := 0
+	for p := 0; p < P; p++ {
+		for s := 0; s < N; s++ {
+			for d := 0; d < N; d++ {
+				if inside[s] && inside[d] {
+					if k < len(inner) && inner[k].Probe == p && inner[k].Src == s && inner[k].Dst == d {
+						changes = append(changes, inner[k])
+						k++
+					}
+				} else if was := base[(p*N+s)*N+d]; was != aclengine.ConnActionFailure {
+					changes = append(changes, ReachChange{Probe: p, Src: s, Dst: d, Was: was,
+						Now: aclengine.ConnActionFailure})
+				}
+			}
+		}
+	}
+	return out, changes, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

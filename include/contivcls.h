@@ -45,6 +45,9 @@ extern "C" {
  *    distinct devices an engine without RCCL keeps host-summed counters;
  *    cls_classify_rules (the per-packet matched-rule trace); CLS_F_DEVICE
  *    connection batches are stream-ordered. */
+/* 5 (additive): cls_reach_matrix; cls_reach_diff (the changed cells of a
+ *    reachability matrix against a baseline: cls_reach_change,
+ *    cls_reach_diff_out). */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -418,6 +421,59 @@ typedef struct cls_reach_spec {
 } cls_reach_spec;
 int cls_reach_matrix(cls_engine* e, const cls_reach_spec* spec, uint8_t* verdict_out,
                      uint64_t* hist_out, uint32_t* allow_out, uint32_t flags, void* stream);
+
+/* ---- reachability diff: the changed cells of a matrix against a baseline --
+ * "What connectivity did this commit change?"  Evaluates the matrix of `spec`
+ * exactly as cls_reach_matrix does (the bindings snapshotted once) and
+ * compares it on the device with `base`, a [P][N][N] matrix of an earlier
+ * call: cell i is changed when base[i] != new[i] (the whole byte).  Neither
+ * matrix has to cross PCIe.  Outputs (cls_reach_diff_out), each optional:
+ *   verdict_out [P][N][N]  the new matrix; NULL, or == base exactly: the
+ *                          baseline is refreshed in place (a tile's verdicts
+ *                          reach it only after its base bytes were compared)
+ *   hist_out, allow_out    of the new matrix, as cls_reach_matrix
+ *   changes, cap           the first min(*n_changes, cap) changed cells in
+ *                          ascending cell index (p N + s) N + d, whatever
+ *                          reach_tile, the evaluator and the scheduling of
+ *                          workgroups; records at and past that count are
+ *                          not written
+ *   n_changes   1 word     all changed cells, also those beyond cap
+ *   trans_out   [P][4][4]  cells of probe p per (base & 3, new), unchanged
+ *                          ones included: row sums are the old histogram,
+ *                          column sums equal hist_out
+ *   changed_out [P][N]     changed cells per (probe, source); overwritten
+ * At least one of changes, n_changes, trans_out, changed_out must be given
+ * (without them the request is cls_reach_matrix); changes needs n_changes
+ * and cap >= 1.  Flags: CLS_F_DEVICE -- base and every output are device
+ * memory (base, verdict_out, changes 16-byte; hist_out, n_changes, trans_out
+ * 8-byte; allow_out, changed_out 4-byte aligned), the call only enqueues on
+ * `stream`, ordered like a device connection batch.  Without it all are host
+ * arrays and the call returns with the results: base goes up tile by tile,
+ * the records come back through an engine-owned buffer, and no caller
+ * pointer is kept.  CLS_F_COUNT, CLS_F_CONN_CLS, CLS_F_FORCE_LINEAR: as
+ * cls_reach_matrix.  CLS_E_INVAL, before any device work and with the
+ * outputs untouched: everything cls_reach_matrix refuses of `spec`, `out` or
+ * `base` NULL, none of the four diff outputs, changes without n_changes or
+ * with cap 0, a misaligned device pointer, verdict_out overlapping base
+ * without being equal to it. */
+typedef struct cls_reach_change {
+    uint32_t probe, src, dst;    /* cell (p, s, d) */
+    uint8_t was, now;            /* the base byte (verbatim), the new ConnectionAction */
+    uint16_t zero;
+} cls_reach_change;              /* 16 bytes, written with one 16-byte store */
+
+typedef struct cls_reach_diff_out {
+    uint8_t* verdict_out;
+    uint64_t* hist_out;
+    uint32_t* allow_out;
+    cls_reach_change* changes;
+    uint64_t cap;
+    uint64_t* n_changes;
+    uint64_t* trans_out;
+    uint32_t* changed_out;
+} cls_reach_diff_out;
+int cls_reach_diff(cls_engine* e, const cls_reach_spec* spec, const uint8_t* base,
+                   const cls_reach_diff_out* out, uint32_t flags, void* stream);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

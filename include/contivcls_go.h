@@ -194,6 +194,69 @@ static inline int clsg_reach_matrix_v16(cls_engine* e, const uint32_t* if_id, co
     return cls_reach_matrix(e, &r, verdict, hist, allow, flags, NULL);
 }
 
+/* cls_reach_diff over IPv4 endpoints: the matrix of clsg_reach_matrix_v4's
+ * arguments against the baseline `base` (n_probes x n x n, of an earlier
+ * call).  Host arrays; verdict (may be base: in place), hist, allow, changes
+ * (cap records of 16 bytes: probe, src, dst as u32, then was, now and two zero
+ * bytes; needs n_changes), n_changes (1), trans (n_probes x 16) and changed
+ * (n_probes x n) may each be NULL, but not all of the last four. */
+static inline int clsg_reach_diff_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                     const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                     uint32_t n_probes, const uint8_t* base, uint8_t* verdict, uint64_t* hist,
+                                     uint32_t* allow, void* changes, uint64_t cap, uint64_t* n_changes,
+                                     uint64_t* trans, uint32_t* changed, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_diff_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.verdict_out = verdict;
+    o.hist_out = hist;
+    o.allow_out = allow;
+    o.changes = (cls_reach_change*)changes;
+    o.cap = cap;
+    o.n_changes = n_changes;
+    o.trans_out = trans;
+    o.changed_out = changed;
+    return cls_reach_diff(e, &r, base, &o, flags, NULL);
+}
+
+/* cls_reach_diff over 16-byte endpoints (n x 16 network-order bytes). */
+static inline int clsg_reach_diff_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                      const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                      uint32_t n_probes, const uint8_t* base, uint8_t* verdict, uint64_t* hist,
+                                      uint32_t* allow, void* changes, uint64_t cap, uint64_t* n_changes,
+                                      uint64_t* trans, uint32_t* changed, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_diff_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.verdict_out = verdict;
+    o.hist_out = hist;
+    o.allow_out = allow;
+    o.changes = (cls_reach_change*)changes;
+    o.cap = cap;
+    o.n_changes = n_changes;
+    o.trans_out = trans;
+    o.changed_out = changed;
+    return cls_reach_diff(e, &r, base, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -22,8 +22,24 @@ more in a child of its own under rocprofv3 --kernel-trace --stats, at the one
 tile size --stats-tile, and adds the average time per launch of reach_expand4
 / reach_expand16, reach_reduce and connect_kernel.
 
+--diff measures the reachability diff (cls_reach_diff) instead: per --locals
+value of --diff-locals, N = 2048 endpoints (--endpoints) x 4 probes, in one
+process it alternates
+
+  A  cls_reach_matrix(CLS_F_DEVICE) with verdicts, histogram and allow counts;
+  B  cls_reach_diff(CLS_F_DEVICE) with the same three outputs plus the changed
+     cells' records (cap 1 Mi), their total, the transition counts and the
+     changed cells per row, against the matrix of the same ACL set with one
+     local ACL deleted and one re-put;
+
+--rounds times --iters calls each, back to back with one wait at the end, and
+prints one JSON line per --locals value: the median ms per call of A and B,
+B / A and the changed cells (checked against a compare of the two matrices).
+
 usage: python tools/reach_bench.py [--af 4|16] [--locals 12] [--endpoints 1024,2048]
            [--tiles 1048576,4194304,16777216] [--iters 9] [--kernel-stats]
+       python tools/reach_bench.py --diff [--af 4|16] [--diff-locals 12,64] [--endpoints 2048]
+           [--iters 9] [--rounds 7]
 """
 import argparse
 import csv
@@ -170,15 +186,102 @@ def measure(a, n):
     return out
 
 
-def kernel_stats(a, n):
+DIFF_CAP = 1 << 20
+
+
+def measure_diff(a, n, n_local):
+    """A / B of cls_reach_matrix and cls_reach_diff on the same engine."""
+    import torch
+    from aclgen import random_acl, random_acl16
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    bind, by_name, ifs, at, addrs, (pr, sp, dp) = setup(eng, a.af, n_local, n)
+    ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
+    cells = N_PROBES * n * n
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    ep_if = np.ascontiguousarray(ids[at], np.uint32)
+    ep_addr = np.ascontiguousarray(addrs, np.uint8 if a.af == 16 else np.uint32)
+    spec = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                          _ptr(ep_addr) if a.af == 16 else None, N_PROBES, _ptr(pr), _ptr(sp), _ptr(dp))
+    base = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    dv = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    dh = torch.empty((N_PROBES, 4), dtype=torch.int64, device="cuda")
+    da = torch.empty((N_PROBES, n), dtype=torch.int32, device="cuda")
+    rec = torch.empty((DIFF_CAP, 4), dtype=torch.int32, device="cuda")
+    total = torch.empty(1, dtype=torch.int64, device="cuda")
+    trans = torch.empty((N_PROBES, 4, 4), dtype=torch.int64, device="cuda")
+    changed = torch.empty((N_PROBES, n), dtype=torch.int32, device="cuda")
+
+    def matrix(v=dv):
+        rc = L.cls_reach_matrix(eng.h, C.byref(spec), _ptr(v), _ptr(dh), _ptr(da), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+    out = _abi.ReachDiffOut(_ptr(dv), _ptr(dh), _ptr(da), _ptr(rec), DIFF_CAP, _ptr(total), _ptr(trans),
+                            _ptr(changed))
+
+    def diff():
+        rc = L.cls_reach_diff(eng.h, C.byref(spec), _ptr(base), C.byref(out), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+
+    def bound(name):
+        return [i for i in ifs if bind[i][0] == name], [i for i in ifs if bind[i][1] == name]
+    # the baseline: one local ACL deleted, one re-put with other rules; then the set as it was
+    gone, reput = "local4", "local9"
+    matrix()
+    sync()
+    first = dv.clone()
+    assert eng.acl_del(gone) == 0
+    assert eng.acl_put(reput, (random_acl16 if a.af == 16 else random_acl)(7001, 40, weird=0.0)[0], *bound(reput)) == 0
+    matrix(base)
+    sync()
+    for name in (gone, reput):
+        assert eng.acl_put(name, by_name[name], *bound(name)) == 0
+    matrix()
+    sync()
+    assert torch.equal(dv, first), "the ACL set was not restored"
+    ta, tb = [], []
+    for _ in range(a.rounds):
+        ta.append(piped(matrix, a.iters, sync))
+        tb.append(piped(diff, a.iters, sync))
+    # parity: the new matrix, the total and the records against a compare of the two matrices
+    sync()
+    assert torch.equal(dv, first), "cls_reach_diff's matrix differs from cls_reach_matrix's"
+    cell = torch.nonzero(base != dv).flatten()
+    n_changed = int(total[0])
+    assert n_changed == cell.numel(), (n_changed, cell.numel())
+    k = min(n_changed, DIFF_CAP)
+    r = rec[:k].to(torch.int64)
+    assert torch.equal((r[:, 0] * n + r[:, 1]) * n + r[:, 2], cell[:k]), "records out of cell order"
+    assert torch.equal(r[:, 3] & 0xFF, base[cell[:k]].to(torch.int64)) and \
+        torch.equal(r[:, 3] >> 8, dv[cell[:k]].to(torch.int64))
+    assert int(trans.sum()) == cells and int(changed.sum()) == n_changed
+    t_a, t_b = float(np.median(ta)), float(np.median(tb))
+    line = {"metric": "reachability diff: B / A (cls_reach_diff(CLS_F_DEVICE) with records (cap 1 Mi), total, "
+                      "transitions and changed-per-row against cls_reach_matrix(CLS_F_DEVICE), the same three "
+                      "matrix outputs, alternated in one process)",
+            "af": a.af, "endpoints": n, "probes": N_PROBES, "cells": cells, "local_acls": n_local,
+            "options": a.opt, "iters": a.iters, "rounds": a.rounds,
+            "A_ms": round(t_a, 4), "B_ms": round(t_b, 4), "B_over_A": round(t_b / t_a, 4),
+            "A_ms_rounds": [round(x, 4) for x in ta], "B_ms_rounds": [round(x, 4) for x in tb],
+            "changed_cells": n_changed,
+            "parity": "matrix == cls_reach_matrix's; total, record order, was / now == compare of the two matrices"}
+    eng.close()
+    return line
+
+
+def kernel_stats(a, n, diff_locals=None):
     """The same measurement in a child under rocprofv3 --kernel-trace --stats
     (a run of its own: the timings above are taken without the profiler):
-    average ns per call of the matrix's kernels and of connect_kernel."""
+    average ns per call of the matrix's kernels and of connect_kernel
+    (diff_locals: of the --diff measurement at that many local ACLs, with the
+    diff's kernels)."""
     with tempfile.TemporaryDirectory() as d:
+        mode = ["--locals", str(a.locals), "--tiles", str(a.stats_tile), "--cpu-sample", "256"]
+        if diff_locals is not None:
+            mode = ["--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
-               sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--locals", str(a.locals),
-               "--endpoints", str(n), "--tiles", str(a.stats_tile), "--iters", str(a.iters),
-               "--cpu-sample", "256"] + [x for o in a.opt for x in ("--opt", o)]
+               sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--endpoints", str(n),
+               "--iters", str(a.iters)] + mode + [x for o in a.opt for x in ("--opt", o)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             return {"error": r.stderr[-400:]}
@@ -188,7 +291,8 @@ def kernel_stats(a, n):
         out = {}
         for row in csv.DictReader(open(files[0])):
             name = row["Name"]
-            for key in ("reach_expand4", "reach_expand16", "reach_reduce", "connect_kernel"):
+            for key in ("reach_expand4", "reach_expand16", "reach_reduce", "reach_diff_count", "reach_diff_scan",
+                        "reach_diff_emit", "connect_kernel"):
                 if key in name:
                     e = out.setdefault(key, {"calls": 0, "total_ns": 0})
                     e["calls"] += int(row["Calls"])
@@ -208,10 +312,23 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=20000, help="cells checked on the oracle (>= 20000)")
     ap.add_argument("--kernel-stats", action="store_true")
     ap.add_argument("--stats-tile", type=int, default=1 << 22, help="the tile size of the --kernel-stats run")
+    ap.add_argument("--diff", action="store_true", help="A / B of cls_reach_matrix and cls_reach_diff")
+    ap.add_argument("--diff-locals", default="12,64")
+    ap.add_argument("--rounds", type=int, default=7, help="--diff: alternations of A and B")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     a.tiles = [int(x) for x in a.tiles.split(",")]
+    if a.diff:
+        for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
+            for n_local in [int(x) for x in a.diff_locals.split(",")]:
+                line = measure_diff(a, n, n_local)
+                if a.kernel_stats and not a.child:
+                    from vpp_amd import _abi
+                    line["kernel_stats"] = dict(kernel_stats(a, n, n_local), sources=_abi.source_hash(),
+                                                note="average per launch over the A and B calls, under the profiler")
+                print(json.dumps(line), flush=True)
+        return
     for n in [int(x) for x in a.endpoints.split(",")]:
         line = measure(a, n)
         if a.kernel_stats and not a.child:

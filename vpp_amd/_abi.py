@@ -11,6 +11,8 @@ import ctypes as C
 import hashlib
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CONTIVCLS_LIB: diagnostics only (A/B timing of kernel build variants)
 LIB_PATH = os.environ.get("CONTIVCLS_LIB") or os.path.join(_HERE, "libcontivcls.so")
@@ -55,7 +57,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_batch_destroy", "cls_batch_shards", "cls_batch_shard", "cls_batch_field", "cls_batch_mirror",
            "cls_batch_upload", "cls_batch_download", "cls_batch_gen_traffic_v4", "cls_batch_gen_traffic_v16",
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
-           "cls_comm_init", "cls_comm_info", "cls_reach_matrix"]
+           "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff"]
 
 
 class ClsRule(C.Structure):
@@ -84,6 +86,24 @@ class ReachSpec(C.Structure):
     _fields_ = [("af", C.c_uint32), ("n_endpoints", C.c_uint32), ("if_id", C.c_void_p), ("addr4", C.c_void_p),
                 ("addr16", C.c_void_p), ("n_probes", C.c_uint32), ("proto", C.c_void_p), ("sport", C.c_void_p),
                 ("dport", C.c_void_p)]
+
+
+class ReachChange(C.Structure):
+    """cls_reach_change: one changed cell, 16 bytes."""
+    _fields_ = [("probe", C.c_uint32), ("src", C.c_uint32), ("dst", C.c_uint32), ("was", C.c_uint8),
+                ("now", C.c_uint8), ("zero", C.c_uint16)]
+
+
+class ReachDiffOut(C.Structure):
+    """cls_reach_diff_out: the outputs of cls_reach_diff, each optional."""
+    _fields_ = [("verdict_out", C.c_void_p), ("hist_out", C.c_void_p), ("allow_out", C.c_void_p),
+                ("changes", C.c_void_p), ("cap", C.c_uint64), ("n_changes", C.c_void_p), ("trans_out", C.c_void_p),
+                ("changed_out", C.c_void_p)]
+
+
+# cls_reach_change as a numpy structured dtype (16 bytes)
+REACH_CHANGE = np.dtype([("probe", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("was", "u1"), ("now", "u1"),
+                         ("zero", "<u2")])
 
 
 class Config(C.Structure):
@@ -212,6 +232,7 @@ def bind(path: str, strict: bool = True):
         "cls_connect_rules": (C.c_int, [vp, C.POINTER(ConnSoa), u64, vp, vp, u32, vp]),
         "cls_conn_counters": (C.c_int, [vp, u32, vp, u32]),
         "cls_reach_matrix": (C.c_int, [vp, C.POINTER(ReachSpec), vp, vp, vp, u32, vp]),
+        "cls_reach_diff": (C.c_int, [vp, C.POINTER(ReachSpec), vp, C.POINTER(ReachDiffOut), u32, vp]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -238,6 +238,11 @@ struct cls_engine {
     // call; reused and grown like the connection scratch (conn_last)
     DevBuf r_tab, r_src, r_dst, r_sif, r_dif, r_sport, r_dport, r_proto, r_verdict, r_hist, r_allow;
     std::vector<uint8_t> reach_up;
+    // cls_reach_diff (reach.cpp), under the same rule: a host call's tile of
+    // baseline bytes and its records, the changed cells per chunk of a tile
+    // and each chunk's first record index, the call's running total (one
+    // u64), the u64 transition and u32 changed-cell accumulators
+    DevBuf r_base, r_changes, r_dcount, r_dbase, r_dtotal, r_trans, r_changed;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

@@ -8,32 +8,12 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "k_reach_dev.hpp"
 #include "kernels.hpp"
 
 namespace cls {
 
 namespace {
-
-// Cell i of the tile: row = rows after the tile's first (probe, source) row,
-// d = its destination.  One 32-bit division per lane; the lane's following
-// cells advance by carries.
-struct ReachCell {
-    uint32_t row, d;
-};
-__device__ __forceinline__ ReachCell reach_cell(const ReachTile& t, uint32_t i) {
-    const uint32_t x = t.d0 + i;                 // < 2^18 + 2^30
-    const uint32_t row = x / t.n_ep;
-    return {row, x - row * t.n_ep};
-}
-// (probe, source) of a row of the tile, relative to the tile's first probe
-struct ReachRow {
-    uint32_t p, s;
-};
-__device__ __forceinline__ ReachRow reach_row(const ReachTile& t, uint32_t row) {
-    const uint32_t y = t.s0 + row;
-    const uint32_t p = y / t.n_ep;
-    return {p, y - p * t.n_ep};
-}
 
 template <bool K16>
 __device__ __forceinline__ void reach_expand_body(const ReachTile& t, const ReachExpand& x) {
@@ -92,13 +72,6 @@ __device__ __forceinline__ void reach_expand_body(const ReachTile& t, const Reac
 }
 __global__ __launch_bounds__(256) void reach_expand4(ReachTile t, ReachExpand x) { reach_expand_body<false>(t, x); }
 __global__ __launch_bounds__(256) void reach_expand16(ReachTile t, ReachExpand x) { reach_expand_body<true>(t, x); }
-
-// sum over the wave's 64 lanes
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kReachBlock) void reach_reduce(ReachTile t, const uint8_t* verdict,
                                                             unsigned long long* hist, uint32_t* allow) {
@@ -191,12 +164,6 @@ __global__ __launch_bounds__(kReachBlock) void reach_reduce(ReachTile t, const u
             atomicAdd(&hist[4ull * pb + threadIdx.x], (unsigned long long)bins[threadIdx.x]);
         __syncthreads();                                           // before the next chunk clears the bins
     }
-}
-
-// memory-bound, grid-stride: at most 8 workgroups per CU
-int reach_grid(uint64_t work, uint32_t per_block, int n_cu) {
-    const uint64_t blocks = (work + per_block - 1) / per_block;
-    return int(std::max<uint64_t>(1, std::min<uint64_t>(blocks, uint64_t(std::max(1, n_cu)) * 8)));
 }
 
 }  // namespace

@@ -407,6 +407,32 @@ constexpr uint32_t kReachBlock = 1024, kReachChunk = 4 * kReachBlock, kReachLdsP
 hipError_t launch_reach_reduce(const ReachTile& t, const uint8_t* verdict, unsigned long long* hist,
                                uint32_t* allow, int n_cu, hipStream_t s);
 
+// ---- the reachability diff (k_reach_diff.hip; contivcls.h cls_reach_diff) -
+// A tile's new verdicts against its baseline bytes (both n bytes, 4-B
+// aligned; a cell is changed when the bytes differ), in three launches whose
+// order comes from a scan -- no workgroup waits for another.  Chunks are the
+// kReachChunk cells a workgroup of reach_reduce takes at a time.
+// count: chunk_count[chunk] = the chunk's changed cells (or null);
+// trans[16 p' + 4 (base & 3) + (now & 3)] += cells (trans at the tile's first
+// probe, or null; binned in LDS like reach_reduce's histogram); changed[r'] +=
+// the row's changed cells (changed at the tile's first (probe, source) row,
+// or null).  A workgroup takes a run of consecutive chunks (at most two
+// workgroups per CU) and adds its bins when a chunk starts in another probe.
+hipError_t launch_reach_diff_count(const ReachTile& t, const uint8_t* base, const uint8_t* now, uint32_t* chunk_count,
+                                   unsigned long long* trans, uint32_t* changed, int n_cu, hipStream_t s);
+// scan (one workgroup): chunk_base[chunk] = *total + the changed cells of the
+// tile's earlier chunks; then *total += the tile's changed cells.
+hipError_t launch_reach_diff_scan(uint32_t n, const uint32_t* chunk_count, unsigned long long* chunk_base,
+                                  unsigned long long* total, hipStream_t s);
+// emit: the tile's changed cells as records {probe, src, dst, was | now << 8}
+// (cls_reach_change, one 16-B store each) at changes[chunk_base[chunk] + the
+// cell's rank in its chunk], while that index is below cap (changes may be
+// null: nothing is emitted).  store: null, or where the tile's new bytes go
+// (the in-place call's matrix; only words that differ are written).
+hipError_t launch_reach_diff_emit(const ReachTile& t, const uint8_t* base, const uint8_t* now,
+                                  const uint32_t* chunk_count, const unsigned long long* chunk_base, uint4* changes,
+                                  unsigned long long cap, uint8_t* store, int n_cu, hipStream_t s);
+
 struct TrafficDev {
     uint64_t seed;
     uint32_t pct_pod, pct_dst, pct_port, pct_icmp;

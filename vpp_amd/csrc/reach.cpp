@@ -6,7 +6,9 @@
 // tile scratch, then per tile of at most reach_tile connections the expand
 // launch (k_reach.hip), connect_locked on the expanded device batch, the
 // reduce launch and a host call's copy back; at the end the accumulators'
-// copy to the outputs.
+// copy to the outputs.  cls_reach_diff is the same call with a baseline: per
+// tile it adds the diff launches (k_reach_diff.hip) behind the reduce launch,
+// and its own outputs at the end.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +36,18 @@ struct ReachCall {
     uint64_t* hist_out = nullptr;
     uint32_t* allow_out = nullptr;
     bool reduce() const { return hist_out || allow_out; }
+    // cls_reach_diff: the baseline (null: cls_reach_matrix) and its outputs;
+    // inplace: verdict_out == base
+    const uint8_t* base = nullptr;
+    bool inplace = false;
+    cls_reach_change* changes = nullptr;
+    uint64_t cap = 0;
+    uint64_t* n_changes = nullptr;
+    uint64_t* trans_out = nullptr;
+    uint32_t* changed_out = nullptr;
+    // the chunk counts and their scan: for the records, the total, and a
+    // device call's in-place stores (made by the emit launch)
+    bool scan() const { return changes || n_changes || (dev && inplace); }
     // the tables' blob (r_tab / reach_up): interface ids at 0, addresses, probes
     size_t off_addr = 0, off_probe = 0, tab_bytes = 0;
 };
@@ -55,8 +69,10 @@ static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdic
     if (!sp->if_id || !(R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4) || !sp->proto || !sp->sport ||
         !sp->dport)
         return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
-    if (!verdict_out && !hist_out && !allow_out) return fail(e, CLS_E_INVAL, "reach matrix without an output");
-    if (!verdict_out && !(flags & CLS_F_NO_VERDICT))
+    // (a diff has outputs of its own, and its verdict_out may simply be NULL)
+    if (!R.base && !verdict_out && !hist_out && !allow_out)
+        return fail(e, CLS_E_INVAL, "reach matrix without an output");
+    if (!R.base && !verdict_out && !(flags & CLS_F_NO_VERDICT))
         return fail(e, CLS_E_INVAL, "verdict_out is NULL without CLS_F_NO_VERDICT");
     R.N = sp->n_endpoints;
     R.P = sp->n_probes;
@@ -80,6 +96,30 @@ static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdic
     R.off_probe = R.off_addr + size_t(R.N) * (R.k16 ? 16 : 4);
     R.off_probe = (R.off_probe + 15) & ~size_t(15);
     R.tab_bytes = R.off_probe + size_t(R.P) * sizeof(uint2);
+    return CLS_OK;
+}
+
+// What cls_reach_diff refuses beyond reach_inputs (which ran: R.cells, R.dev).
+static int reach_diff_inputs(cls_engine* e, const cls_reach_diff_out* o, ReachCall& R) {
+    if (!o->changes && !o->n_changes && !o->trans_out && !o->changed_out)
+        return fail(e, CLS_E_INVAL, "reach diff without changes, n_changes, trans_out or changed_out");
+    if (o->changes && !o->n_changes) return fail(e, CLS_E_INVAL, "reach diff: changes without n_changes");
+    if (o->changes && !o->cap) return fail(e, CLS_E_INVAL, "reach diff: changes with cap 0");
+    if (R.dev && (!aligned(R.base, 16) || !aligned(o->changes, 16) || !aligned(o->n_changes, 8) ||
+                  !aligned(o->trans_out, 8) || !aligned(o->changed_out, 4)))
+        return fail(e, CLS_E_INVAL, "device reach diff: base, changes 16-byte, n_changes, trans_out 8-byte, "
+                                    "changed_out 4-byte aligned");
+    R.inplace = R.verdict_out == R.base;
+    if (R.verdict_out && !R.inplace) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(R.base), b = reinterpret_cast<uintptr_t>(R.verdict_out);
+        if (a < b + R.cells && b < a + R.cells)
+            return fail(e, CLS_E_INVAL, "reach diff: verdict_out overlaps base without being equal to it");
+    }
+    R.changes = o->changes;
+    R.cap = o->changes ? o->cap : 0;
+    R.n_changes = o->n_changes;
+    R.trans_out = o->trans_out;
+    R.changed_out = o->changed_out;
     return CLS_OK;
 }
 
@@ -118,7 +158,7 @@ static int reach_scratch(cls_engine* e, const ReachCall& R) {
     HIPC(e, reach_grow(e, e->r_sif, n * 4)); HIPC(e, reach_grow(e, e->r_dif, n * 4));
     HIPC(e, reach_grow(e, e->r_sport, n * 2)); HIPC(e, reach_grow(e, e->r_dport, n * 2));
     HIPC(e, reach_grow(e, e->r_proto, n));
-    if (!R.dev || !R.verdict_out) HIPC(e, reach_grow(e, e->r_verdict, n));
+    if (!R.dev || !R.verdict_out || R.inplace) HIPC(e, reach_grow(e, e->r_verdict, n));
     if (R.hist_out) {
         HIPC(e, reach_grow(e, e->r_hist, size_t(R.P) * 4 * 8));
         HIPC(e, hipMemsetAsync(e->r_hist.p, 0, size_t(R.P) * 4 * 8, R.s));
@@ -127,6 +167,58 @@ static int reach_scratch(cls_engine* e, const ReachCall& R) {
         HIPC(e, reach_grow(e, e->r_allow, size_t(R.P) * R.N * 4));
         HIPC(e, hipMemsetAsync(e->r_allow.p, 0, size_t(R.P) * R.N * 4, R.s));
     }
+    return CLS_OK;
+}
+
+// The diff's scratch: a host call's tile of baseline bytes and its records
+// (min(cap, P N^2) of them), the tile's chunk counts and first indices, the
+// running total and the accumulators (cleared).
+static int reach_diff_scratch(cls_engine* e, const ReachCall& R) {
+    const size_t n = size_t((std::min(R.tile, R.cells) + 3) & ~uint64_t(3));
+    if (!R.dev) HIPC(e, reach_grow(e, e->r_base, n));
+    if (!R.dev && R.changes)
+        HIPC(e, reach_grow(e, e->r_changes, size_t(std::min(R.cap, R.cells)) * sizeof(cls_reach_change)));
+    if (R.scan()) {
+        const size_t chunks = (n + kReachChunk - 1) / kReachChunk;
+        HIPC(e, reach_grow(e, e->r_dcount, chunks * 4));
+        HIPC(e, reach_grow(e, e->r_dbase, chunks * 8));
+        HIPC(e, reach_grow(e, e->r_dtotal, 8));
+        HIPC(e, hipMemsetAsync(e->r_dtotal.p, 0, 8, R.s));
+    }
+    if (R.trans_out) {
+        HIPC(e, reach_grow(e, e->r_trans, size_t(R.P) * 16 * 8));
+        HIPC(e, hipMemsetAsync(e->r_trans.p, 0, size_t(R.P) * 16 * 8, R.s));
+    }
+    if (R.changed_out) {
+        HIPC(e, reach_grow(e, e->r_changed, size_t(R.P) * R.N * 4));
+        HIPC(e, hipMemsetAsync(e->r_changed.p, 0, size_t(R.P) * R.N * 4, R.s));
+    }
+    return CLS_OK;
+}
+
+// The tile's verdicts v against its baseline bytes: count, then -- for the
+// records, the total or an in-place call's stores -- scan and emit.  A host
+// call's baseline tile goes up into scratch first.
+static int reach_diff_tile(cls_engine* e, const ReachCall& R, const ReachTile& T, uint64_t first, uint64_t row,
+                           const uint8_t* v) {
+    const uint8_t* base = R.base + first;
+    if (!R.dev) {
+        HIPC(e, hipMemcpyAsync(e->r_base.p, base, T.n, hipMemcpyHostToDevice, R.s));
+        base = e->r_base.as<uint8_t>();
+    }
+    uint32_t* count = R.scan() ? e->r_dcount.as<uint32_t>() : nullptr;
+    HIPC(e, launch_reach_diff_count(T, base, v, count,
+                                    R.trans_out ? e->r_trans.as<unsigned long long>() + 16 * uint64_t(T.p0) : nullptr,
+                                    R.changed_out ? e->r_changed.as<uint32_t>() + row : nullptr, e->n_cu, R.s));
+    if (!R.scan()) return CLS_OK;
+    unsigned long long* at = e->r_dbase.as<unsigned long long>();
+    HIPC(e, launch_reach_diff_scan((T.n + kReachChunk - 1) / kReachChunk, count, at,
+                                   e->r_dtotal.as<unsigned long long>(), R.s));
+    // the caller's device records, or the engine's (the cells past the buffer's
+    // min(cap, P N^2) records are past cap)
+    cls_reach_change* rec = R.dev ? R.changes : R.changes ? e->r_changes.as<cls_reach_change>() : nullptr;
+    HIPC(e, launch_reach_diff_emit(T, base, v, count, at, reinterpret_cast<uint4*>(rec), R.cap,
+                                   R.dev && R.inplace ? R.verdict_out + first : nullptr, e->n_cu, R.s));
     return CLS_OK;
 }
 
@@ -155,13 +247,41 @@ static int reach_tile(cls_engine* e, const ReachCall& R, uint64_t first, uint32_
     }
     c.pkt.sport = X.sport; c.pkt.dport = X.dport; c.pkt.proto = X.proto;
     c.src_if = X.src_if; c.dst_if = X.dst_if;
-    uint8_t* v = R.dev && R.verdict_out ? R.verdict_out + first : e->r_verdict.as<uint8_t>();
+    // (an in-place diff's verdicts reach the matrix behind the compare)
+    uint8_t* v = R.dev && R.verdict_out && !R.inplace ? R.verdict_out + first : e->r_verdict.as<uint8_t>();
     const int rc = connect_locked(e, &c, n, v, CLS_F_DEVICE | R.mode, R.s, false);
     if (rc != CLS_OK) return rc;
     if (R.reduce())
         HIPC(e, launch_reach_reduce(T, v, R.hist_out ? e->r_hist.as<unsigned long long>() + 4 * uint64_t(T.p0) : nullptr,
                                     R.allow_out ? e->r_allow.as<uint32_t>() + row : nullptr, e->n_cu, R.s));
+    if (R.base) {
+        const int drc = reach_diff_tile(e, R, T, first, row, v);
+        if (drc != CLS_OK) return drc;
+    }
     if (!R.dev && R.verdict_out) HIPC(e, hipMemcpyAsync(R.verdict_out + first, v, n, hipMemcpyDeviceToHost, R.s));
+    return CLS_OK;
+}
+
+// The diff's accumulators and total to the caller's outputs; a host call
+// waits for the total and copies that many of its records (none past them).
+static int reach_diff_outputs(cls_engine* e, const ReachCall& R) {
+    const hipMemcpyKind kind = R.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (R.trans_out) HIPC(e, hipMemcpyAsync(R.trans_out, e->r_trans.p, size_t(R.P) * 16 * 8, kind, R.s));
+    if (R.changed_out) HIPC(e, hipMemcpyAsync(R.changed_out, e->r_changed.p, size_t(R.P) * R.N * 4, kind, R.s));
+    if (!R.n_changes) return CLS_OK;
+    if (R.dev) {
+        HIPC(e, hipMemcpyAsync(R.n_changes, e->r_dtotal.p, 8, kind, R.s));
+        return CLS_OK;
+    }
+    uint64_t total = 0;
+    HIPC(e, hipMemcpyAsync(&total, e->r_dtotal.p, 8, kind, R.s));
+    HIPC(e, hipStreamSynchronize(R.s));
+    const uint64_t n = std::min(total, R.cap);
+    if (R.changes && n) {
+        HIPC(e, hipMemcpyAsync(R.changes, e->r_changes.p, size_t(n) * sizeof(cls_reach_change), kind, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+    }
+    *R.n_changes = total;
     return CLS_OK;
 }
 
@@ -191,6 +311,26 @@ extern "C" int cls_reach_matrix(cls_engine* e, const cls_reach_spec* spec, uint8
     if (rc == CLS_OK) rc = reach_scratch(e, R);
     for (uint64_t first = 0; rc == CLS_OK && first < R.cells; first += R.tile)
         rc = reach_tile(e, R, first, uint32_t(std::min(R.tile, R.cells - first)));
+    if (rc == CLS_OK) rc = reach_outputs(e, R);
+    return rc;
+}
+
+extern "C" int cls_reach_diff(cls_engine* e, const cls_reach_spec* spec, const uint8_t* base,
+                              const cls_reach_diff_out* out, uint32_t flags, void* stream) {
+    if (!e || !spec) return CLS_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    if (!base || !out) return fail(e, CLS_E_INVAL, "reach diff without a baseline or outputs");
+    ReachCall R;
+    R.base = base;
+    int rc = reach_inputs(e, spec, out->verdict_out, out->hist_out, out->allow_out, flags, stream, R);
+    if (rc == CLS_OK) rc = reach_diff_inputs(e, out, R);
+    if (rc == CLS_OK) rc = reach_upload(e, spec, R);
+    if (rc == CLS_OK) rc = reach_scratch(e, R);
+    if (rc == CLS_OK) rc = reach_diff_scratch(e, R);
+    for (uint64_t first = 0; rc == CLS_OK && first < R.cells; first += R.tile)
+        rc = reach_tile(e, R, first, uint32_t(std::min(R.tile, R.cells - first)));
+    if (rc == CLS_OK) rc = reach_diff_outputs(e, R);
     if (rc == CLS_OK) rc = reach_outputs(e, R);
     return rc;
 }

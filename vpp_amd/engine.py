@@ -15,6 +15,7 @@ would: the protobuf ACLs by name, pods and interface names.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import weakref
 from typing import Optional
@@ -29,6 +30,10 @@ ACL_KEY_PREFIX = "vpp/config/v1/acl/"
 CONN_DENY_SYN, CONN_DENY_SYN_ACK, CONN_ALLOW, CONN_FAILURE = 0, 1, 2, 3
 # ProtocolType (aclengine_mock.go:80-91)
 TCP, UDP, ICMP = 0, 1, 2
+
+
+# Engine.reach_diff's result; what was not asked for is None
+ReachDiff = collections.namedtuple("ReachDiff", "verdicts changes n_changes trans changed hist allow")
 
 
 def _is_torch(x) -> bool:
@@ -579,6 +584,98 @@ class Engine:
                                                 flags, s))
         return tuple(res)
 
+    def reach_diff(self, if_ids, addrs, protos, sports, dports, base, cap=None, mode: str = "auto",
+                   count: bool = False, verdicts: bool = True, hist: bool = False, allow: bool = False,
+                   trans: bool = True, changed: bool = True, inplace: bool = False, out=None, stream=None):
+        """The reachability matrix of reach_matrix's arguments against a
+        baseline (cls_reach_diff): ``base`` is the [P, N, N] u8 matrix of an
+        earlier call, compared on the device.  Returns ReachDiff(verdicts
+        [P, N, N] u8: the new matrix, changes: the changed cells in cell
+        order, n_changes: all of them, also beyond ``cap``, trans [P, 4, 4]
+        u64: cells per (base & 3, new), changed [P, N] u32: changed cells per
+        (probe, source), hist, allow: as reach_matrix); what is not wanted is
+        None.  ``cap``: the records kept (None: P N^2, or the rows of the
+        caller's ``changes`` tensor); 0: no records, and n_changes only when
+        neither trans nor changed is wanted.  ``inplace``: the new matrix
+        replaces ``base`` (returned as verdicts).  A numpy ``base`` selects
+        the host form: the call returns with numpy results, changes a
+        structured array (_abi.REACH_CHANGE) cut to min(n_changes, cap) and
+        n_changes an int.  A torch GPU uint8 ``base`` selects the device form:
+        changes is an int32 [cap, 4] tensor of (probe, src, dst, was | now <<
+        8) rows, of which the first min(n_changes, cap) are written,
+        n_changes an int64 [1] tensor; ``out``, a ReachDiff or a sequence in
+        its order, gives the caller's tensors (None for a wanted one
+        allocates it), and the call only enqueues on ``stream`` (default: the
+        engine's)."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        if count:
+            flags |= _abi.F_COUNT
+        if not (verdicts or inplace):
+            flags |= _abi.F_NO_VERDICT
+        ids = np.ascontiguousarray(if_ids, np.uint32)
+        a = np.asarray(addrs)
+        v16 = a.ndim == 2
+        a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+        pr, sp = np.ascontiguousarray(protos, np.uint8), np.ascontiguousarray(sports, np.uint16)
+        dp = np.ascontiguousarray(dports, np.uint16)
+        n, p = len(ids), len(pr)
+        if len(a) != n or len(sp) != p or len(dp) != p:
+            raise ClsError("reach diff: N interface ids and addresses, P protocols and ports")
+        spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                              _ptr(a) if v16 else None, p, _ptr(pr), _ptr(sp), _ptr(dp))
+        dev = _is_torch(base)
+        given = [None] * 7 if out is None else list(out)
+        if len(given) != 7 or (not dev and out is not None):
+            raise ClsError("reach diff: out is a ReachDiff of GPU tensors, for a GPU base")
+        if cap is None:
+            cap = given[1].shape[0] if given[1] is not None else p * n * n
+        cap = int(cap)
+        listed = cap > 0 or not (trans or changed)
+        # (verdicts, changes, n_changes, trans, changed, hist, allow): wanted, shape
+        want = (verdicts and not inplace, cap > 0, listed, trans, changed, hist, allow)
+        shapes = ((p, n, n), (cap, 4), (1,), (p, 4, 4), (p, n), (p, 4), (p, n))
+        if dev:
+            import torch
+            flags |= _abi.F_DEVICE
+            if not (base.is_cuda and base.is_contiguous() and base.dtype == torch.uint8 and
+                    tuple(base.shape) == (p, n, n)):
+                raise ClsError("reach diff: base must be a contiguous uint8 GPU tensor of shape (P, N, N)")
+            kinds = ((torch.uint8, 1), (torch.int32, 4), (torch.int64, 8), (torch.int64, 8), (torch.int32, 4),
+                     (torch.int64, 8), (torch.int32, 4))
+            res = []
+            for k, (w, sh, (dt, sz)) in enumerate(zip(want, shapes, kinds)):
+                t = given[k] if w else None
+                if w and t is None:
+                    t = torch.empty(sh, dtype=dt, device=base.device)
+                elif w and not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.element_size() == sz and
+                                tuple(t.shape) == sh):
+                    raise ClsError("reach diff: out.%s must be a contiguous GPU tensor of shape %s, %d-byte elements"
+                                   % (ReachDiff._fields[k], sh, sz))
+                res.append(t)
+            s = None
+            if stream is not None:
+                s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        else:
+            base = np.asarray(base)
+            if not (base.dtype == np.uint8 and base.shape == (p, n, n) and base.flags.c_contiguous and
+                    (base.flags.writeable or not inplace)):
+                raise ClsError("reach diff: base must be a contiguous uint8 array of shape (P, N, N)")
+            kinds = (np.uint8, np.int32, np.uint64, np.uint64, np.uint32, np.uint64, np.uint32)
+            res = [np.zeros(sh, dt) if w else None for w, sh, dt in zip(want, shapes, kinds)]
+            if res[1] is not None:
+                res[1] = np.zeros(min(cap, p * n * n), _abi.REACH_CHANGE)
+            s = None
+        if inplace:
+            res[0] = base
+        o = _abi.ReachDiffOut(_ptr(res[0]), _ptr(res[5]), _ptr(res[6]), _ptr(res[1]), cap if res[1] is not None else 0,
+                              _ptr(res[2]), _ptr(res[3]), _ptr(res[4]))
+        self._check(_abi.lib().cls_reach_diff(self.h, C.byref(spec), _ptr(base), C.byref(o), flags, s))
+        if not dev and res[2] is not None:
+            res[2] = int(res[2][0])
+            if res[1] is not None:
+                res[1] = res[1][:min(res[2], cap)]
+        return ReachDiff(*res)
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -920,6 +1017,28 @@ class ACLEngine:
             out[i] = int(v)
         return out
 
+    def _matrix_endpoints(self, pods):
+        """(index in pods, interface id, net.IP) of the pods that reach
+        testConnection (connection_matrix)."""
+        eps = []
+        for i, pod in enumerate(pods):
+            cfg = self.pods.get(pod)
+            ifn = self._pod_if(pod, cfg) if cfg is not None else None
+            if ifn is not None:
+                eps.append((i, self.engine.if_id(ifn), cfg[0]))
+        return eps
+
+    @staticmethod
+    def _matrix_addrs(eps):
+        """The endpoints' addresses: u32 when all are IPv4, else (n, 16) bytes."""
+        four = [_ip4(ip) for _, _, ip in eps]
+        if all(a is not None for a in four):
+            return np.array(four, np.uint32)
+        a16 = [_ip16(ip) for _, _, ip in eps]
+        if any(a is None for a in a16):
+            raise ClsError("connection endpoint is not an IPv4 or IPv6 address")
+        return np.frombuffer(b"".join(a16), np.uint8).reshape(-1, 16)
+
     def connection_matrix(self, pods, probes, count: bool = False) -> np.ndarray:
         """Who reaches whom: a [len(probes), len(pods), len(pods)] uint8 array
         whose cell (p, s, d) equals connection_pod_to_pod(pods[s], pods[d],
@@ -931,28 +1050,50 @@ class ACLEngine:
         are CONN_FAILURE.  The IPv4 layout when every endpoint is IPv4, else
         the 16-byte layout.  count: as connection_batch."""
         out = np.full((len(probes), len(pods), len(pods)), CONN_FAILURE, np.uint8)
-        eps = []                                    # (index in pods, interface id, net.IP)
-        for i, pod in enumerate(pods):
-            cfg = self.pods.get(pod)
-            ifn = self._pod_if(pod, cfg) if cfg is not None else None
-            if ifn is not None:
-                eps.append((i, self.engine.if_id(ifn), cfg[0]))
+        eps = self._matrix_endpoints(pods)
         if not eps or not probes:
             return out
-        four = [_ip4(ip) for _, _, ip in eps]
-        if all(a is not None for a in four):
-            addrs = np.array(four, np.uint32)
-        else:
-            a16 = [_ip16(ip) for _, _, ip in eps]
-            if any(a is None for a in a16):
-                raise ClsError("connection endpoint is not an IPv4 or IPv6 address")
-            addrs = np.frombuffer(b"".join(a16), np.uint8).reshape(-1, 16)
+        addrs = self._matrix_addrs(eps)
         pr = np.array(probes, np.int64).reshape(-1, 3)
         v, _, _ = self.engine.reach_matrix([e[1] for e in eps], addrs, pr[:, 0], pr[:, 1], pr[:, 2], count=count,
                                            hist=False, allow=False)
         at = np.array([e[0] for e in eps])
         out[:, at[:, None], at[None, :]] = v
         return out
+
+    def connection_matrix_diff(self, pods, probes, base, count: bool = False):
+        """connection_matrix against a baseline: (matrix, changes), matrix
+        what connection_matrix(pods, probes) returns and changes the cells
+        where it differs from ``base`` -- a [len(probes), len(pods),
+        len(pods)] uint8 array, such as the matrix of an earlier commit -- as
+        (probe index, src pod, dst pod, was, now) in cell order over ``pods``.
+        One engine call (Engine.reach_diff) over the resolvable endpoints,
+        which sees ``base`` restricted to them; the rows and columns of the
+        pods left out are compared here against CONN_FAILURE."""
+        base = np.asarray(base, np.uint8)
+        if base.shape != (len(probes), len(pods), len(pods)):
+            raise ClsError("connection matrix diff: base must have shape (probes, pods, pods)")
+        out = np.full(base.shape, CONN_FAILURE, np.uint8)
+        eps = self._matrix_endpoints(pods)
+        cells = []                                  # (probe, src, dst, was, now), indices into pods
+        if eps and probes:
+            addrs = self._matrix_addrs(eps)
+            pr = np.array(probes, np.int64).reshape(-1, 3)
+            at = np.array([e[0] for e in eps])
+            sub = np.ascontiguousarray(base[:, at[:, None], at[None, :]])
+            r = self.engine.reach_diff([e[1] for e in eps], addrs, pr[:, 0], pr[:, 1], pr[:, 2], sub, count=count,
+                                       trans=False, changed=False)
+            out[:, at[:, None], at[None, :]] = r.verdicts
+            cells = [(int(c["probe"]), int(at[c["src"]]), int(at[c["dst"]]), int(c["was"]), int(c["now"]))
+                     for c in r.changes]
+        # the pods left out: every cell of their rows and columns is CONN_FAILURE
+        rest = np.ones(len(pods), bool)
+        rest[[e[0] for e in eps]] = False
+        outside = rest[:, None] | rest[None, :]
+        cells += [(int(p), int(s), int(d), int(base[p, s, d]), CONN_FAILURE)
+                  for p, s, d in np.argwhere((base != CONN_FAILURE) & outside[None])]
+        cells.sort(key=lambda c: c[:3])
+        return out, [(p, pods[s], pods[d], was, now) for p, s, d, was, now in cells]
 
     def connection_pod_to_pod(self, src_pod, dst_pod, proto, sport, dport):
         return self.connection_batch([("ConnectionPodToPod", (src_pod, dst_pod, proto, sport, dport))])[0]
