@@ -876,6 +876,126 @@ func (en *Engine) ReachDiff(pods []podmodel.ID, probes []Probe, base []aclengine
 	return out, changes, nil
 }
 
+// PortRange is one maximal range of ReachPorts: ConnectionPodToPod(pods[Src],
+// pods[Dst], protocol, srcPort, port) returns Action for every destination
+// port in [Lo, Hi].
+type PortRange struct {
+	Src, Dst int
+	Lo, Hi   uint16
+	Action   aclengine.ConnectionAction
+}
+
+// ReachPorts answers "on which destination ports does pod s reach pod d?" for
+// all 65,536 ports in one engine call (cls_reach_ports): the engine evaluates
+// one representative port per port class of the bound ACLs and returns only
+// the maximal ranges, in (Src, Dst, Lo) order, the ranges of a pair covering
+// 0..65535; runs[s*N+d] is the number of ranges of the pair.  Pods that
+// ConnectionPodToPod fails before testConnection stay out of the call: their
+// pairs are the one range 0..65535 of ConnActionFailure.
+func (en *Engine) ReachPorts(pods []podmodel.ID, protocol aclengine.ProtocolType, srcPort uint16) ([]PortRange,
+	[]uint32, error) {
+	en.Lock()
+	defer en.Unlock()
+	N := len(pods)
+	runs := make([]uint32, N*N)
+	for i := range runs {
+		runs[i] = 1
+	}
+	var strs cstrs
+	defer strs.free()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	inside := make([]bool, N)
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil {
+			continue
+		}
+		ifName, ok := en.podIf(pod, cfg)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		inside[i] = true
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	var rec []uint32 // 16-byte records: src, dst, lo | hi << 16, action
+	total := 0
+	if n > 0 {
+		a4 := make([]uint32, n)
+		a16 := make([]byte, 16*n)
+		for k := 0; k < n; k++ {
+			if v4 {
+				a := ips[k].To4()
+				a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+			} else {
+				a := ips[k].To16()
+				if a == nil {
+					return nil, nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+				}
+				copy(a16[16*k:], a)
+			}
+		}
+		// every slice goes to the shim as its own pointer (pointer-free Go
+		// memory); the shim builds both structs on the C stack.  The ranges
+		// are counted first, then fetched.
+		inner := make([]uint32, n*n)
+		var count C.uint64_t
+		for pass := 0; pass < 2; pass++ {
+			var buf unsafe.Pointer
+			var irun *C.uint32_t
+			if pass == 1 {
+				rec = make([]uint32, 4*int(count))
+				buf = unsafe.Pointer(&rec[0])
+				irun = (*C.uint32_t)(&inner[0])
+			}
+			var rc C.int
+			if v4 {
+				rc = C.clsg_reach_ports_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+					C.uint8_t(protocol), C.uint16_t(srcPort), buf, count, &count, irun, nil, nil, nil, 0)
+			} else {
+				rc = C.clsg_reach_ports_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+					C.uint8_t(protocol), C.uint16_t(srcPort), buf, count, &count, irun, nil, nil, nil, 0)
+			}
+			if rc != C.CLS_OK {
+				return nil, nil, en.lastErr()
+			}
+		}
+		total = len(rec) / 4
+		if int(count) < total { // (the bindings cannot change under the lock)
+			total = int(count)
+		}
+		for s := 0; s < n; s++ {
+			for d := 0; d < n; d++ {
+				runs[at[s]*N+at[d]] = inner[s*n+d]
+			}
+		}
+	}
+	// merge, in pair order, with the pairs of the pods left out (at is
+	// ascending, so the engine's records are in pair order over pods too)
+	var out []PortRange
+	k := 0
+	for s := 0; s < N; s++ {
+		for d := 0; d < N; d++ {
+			if !inside[s] || !inside[d] {
+				out = append(out, PortRange{Src: s, Dst: d, Lo: 0, Hi: 65535, Action: aclengine.ConnActionFailure})
+				continue
+			}
+			for k < total && at[rec[4*k]] == s && at[rec[4*k+1]] == d {
+				out = append(out, PortRange{Src: s, Dst: d, Lo: uint16(rec[4*k+2] & 0xFFFF),
+					Hi: uint16(rec[4*k+2] >> 16), Action: aclengine.ConnectionAction(rec[4*k+3] & 0xFF)})
+				k++
+			}
+		}
+	}
+	return out, runs, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

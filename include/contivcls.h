@@ -47,7 +47,9 @@ extern "C" {
  *    connection batches are stream-ordered. */
 /* 5 (additive): cls_reach_matrix; cls_reach_diff (the changed cells of a
  *    reachability matrix against a baseline: cls_reach_change,
- *    cls_reach_diff_out). */
+ *    cls_reach_diff_out); cls_reach_ports (per-pair port ranges over all
+ *    65,536 destination ports: cls_port_range, cls_reach_ports_out) and
+ *    cls_port_classes. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -474,6 +476,74 @@ typedef struct cls_reach_diff_out {
 } cls_reach_diff_out;
 int cls_reach_diff(cls_engine* e, const cls_reach_spec* spec, const uint8_t* base,
                    const cls_reach_diff_out* out, uint32_t flags, void* stream);
+
+/* ---- reachability port sweep: per-pair port ranges over all 65,536 ports --
+ * "On which destination ports does s reach d?"  Cell (s, d, port) is
+ * testConnection(if_id[s], addr[s], if_id[d], addr[d], proto, sport, port)
+ * for every port 0..65535, with `spec` as in cls_reach_matrix but exactly one
+ * probe (proto[0], sport[0]; dport is ignored and may be NULL); the bindings
+ * are snapshotted once, the diagonal and same-interface pairs included.
+ * evalACL (:527-643) sees the destination port only in comparisons with
+ * uint16(LowerPort) / uint16(UpperPort) of TCP / UDP rules, so a pair's
+ * ConnectionAction is constant on every port class: the elementary intervals
+ * whose starts are {0}, lo16 and hi16 + 1 of the swept protocol's rules over
+ * the ACLs bound to the endpoints' interfaces (K classes).  The engine
+ * evaluates one representative per class -- K N^2 connections, rows
+ * (s N + d) K + k in tiles of whole pairs -- and compresses them on the
+ * device.  Outputs (cls_reach_ports_out), each optional:
+ *   ranges, cap   the first min(*n_ranges, cap) maximal ranges (adjacent
+ *                 classes of equal action merged) in ascending (src, dst,
+ *                 port_lo) order; the ranges of one pair tile [0, 65535].
+ *                 Canonical: they depend on the verdicts alone, not on the
+ *                 classes, reach_tile, the evaluator or the scheduling.
+ *                 Records at and past that count are not written
+ *   n_ranges      1 word: all ranges, also those beyond cap
+ *   runs_out        [N][N]  ranges of the pair
+ *   allow_ports_out [N][N]  dports with CLS_CONN_ALLOW, 0 .. 65536
+ *   hist_out        [4]     (pair, dport) cells per ConnectionAction (sum 65536 N^2)
+ *   n_classes     HOST word, also with CLS_F_DEVICE: K, written before the
+ *                 call returns
+ * At least one of ranges, n_ranges, runs_out, allow_ports_out, hist_out must
+ * be given; ranges needs n_ranges and cap >= 1.  Any protocol is accepted:
+ * for anything but TCP / UDP no rule tests the port, K = 1 and every pair has
+ * the one range 0..65535.  Flags: CLS_F_DEVICE -- every output but n_classes
+ * is device memory (ranges 16-byte, n_ranges and hist_out 8-byte, runs_out
+ * and allow_ports_out 4-byte aligned) and the call only enqueues on `stream`,
+ * ordered like a device connection batch; without it they are host arrays,
+ * filled through engine-owned buffers (no caller pointer is kept).
+ * CLS_F_CONN_CLS, CLS_F_FORCE_LINEAR: as cls_reach_matrix.  CLS_E_INVAL,
+ * before any device work and with the outputs untouched: everything
+ * cls_reach_matrix refuses of `spec` (but the NULL dport), n_probes != 1,
+ * `out` NULL, no output, ranges without n_ranges or with cap 0, a misaligned
+ * device pointer, CLS_F_COUNT or CLS_F_NO_VERDICT (representatives are
+ * evaluated: connection counters would mean nothing), K N^2 > 2^36 (K and N
+ * in cls_last_error).  On a multi-device engine the call runs on the first
+ * device. */
+typedef struct cls_port_range {  /* 16 bytes */
+    uint32_t src, dst;           /* endpoint indices */
+    uint16_t port_lo, port_hi;   /* inclusive */
+    uint8_t action;              /* ConnectionAction for every dport in [port_lo, port_hi] */
+    uint8_t zero[3];
+} cls_port_range;
+
+typedef struct cls_reach_ports_out {
+    cls_port_range* ranges;
+    uint64_t cap;
+    uint64_t* n_ranges;
+    uint32_t* runs_out;
+    uint32_t* allow_ports_out;
+    uint64_t* hist_out;
+    uint32_t* n_classes;
+} cls_reach_ports_out;
+int cls_reach_ports(cls_engine* e, const cls_reach_spec* spec, const cls_reach_ports_out* out,
+                    uint32_t flags, void* stream);
+/* The class starts of one rule list for `proto` (no device needed): ascending,
+ * lo_out[0] == 0, each in {0}, lo16 or hi16 + 1 <= 65535 of the rules that
+ * carry a destination range for `proto` (the u16 values evalACL compares
+ * with); K = 1 for anything but TCP / UDP.  *n = K; with cap < K only *n is
+ * set.  cls_reach_ports uses the sorted union over the bound ACLs. */
+int cls_port_classes(const cls_rule* rules, uint32_t n_rules, uint32_t proto,
+                     uint16_t* lo_out, uint32_t cap, uint32_t* n);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

@@ -257,6 +257,63 @@ static inline int clsg_reach_diff_v16(cls_engine* e, const uint32_t* if_id, cons
     return cls_reach_diff(e, &r, base, &o, flags, NULL);
 }
 
+/* cls_reach_ports over IPv4 endpoints: per-pair port ranges over all 65,536
+ * destination ports for one protocol and source port.  Host arrays; ranges
+ * (cap records of 16 bytes: src, dst as u32, port_lo, port_hi as u16, the
+ * action and three zero bytes; needs n_ranges), n_ranges (1), runs and
+ * allow_ports (n x n each) and hist (4) may each be NULL, but not all;
+ * n_classes (1) may be NULL. */
+static inline int clsg_reach_ports_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                      uint8_t proto, uint16_t sport, void* ranges, uint64_t cap, uint64_t* n_ranges,
+                                      uint32_t* runs, uint32_t* allow_ports, uint64_t* hist, uint32_t* n_classes,
+                                      uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_ports_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = 1;
+    r.proto = &proto;
+    r.sport = &sport;
+    memset(&o, 0, sizeof o);
+    o.ranges = (cls_port_range*)ranges;
+    o.cap = cap;
+    o.n_ranges = n_ranges;
+    o.runs_out = runs;
+    o.allow_ports_out = allow_ports;
+    o.hist_out = hist;
+    o.n_classes = n_classes;
+    return cls_reach_ports(e, &r, &o, flags, NULL);
+}
+
+/* cls_reach_ports over 16-byte endpoints (n x 16 network-order bytes). */
+static inline int clsg_reach_ports_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                       uint8_t proto, uint16_t sport, void* ranges, uint64_t cap, uint64_t* n_ranges,
+                                       uint32_t* runs, uint32_t* allow_ports, uint64_t* hist, uint32_t* n_classes,
+                                       uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_ports_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = 1;
+    r.proto = &proto;
+    r.sport = &sport;
+    memset(&o, 0, sizeof o);
+    o.ranges = (cls_port_range*)ranges;
+    o.cap = cap;
+    o.n_ranges = n_ranges;
+    o.runs_out = runs;
+    o.allow_ports_out = allow_ports;
+    o.hist_out = hist;
+    o.n_classes = n_classes;
+    return cls_reach_ports(e, &r, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -36,10 +36,28 @@ process it alternates
 prints one JSON line per --locals value: the median ms per call of A and B,
 B / A and the changed cells (checked against a compare of the two matrices).
 
+--ports measures the port sweep (cls_reach_ports) instead: per --locals value
+of --diff-locals it computes the K port classes of the TCP sweep over the
+endpoints' ACLs (Engine.port_classes), takes the largest N of 2048, 1024, 512,
+256 with K N^2 <= 2^32 rows (a call then stays well under a second) and in one
+process alternates
+
+  A  what a caller can do without the call: cls_reach_matrix(CLS_F_DEVICE,
+     verdicts to HBM) with P = K probes at the class starts -- K N^2 bytes
+     that are still to be downloaded and run-length encoded on the host;
+  B  cls_reach_ports(CLS_F_DEVICE) with the ranges (cap: their total), the
+     total, the runs and ALLOW ports per pair and the histogram;
+
+and prints one JSON line: the median ms per call of A and B, B / A, K, the
+ranges and the bytes each leaves to download (B's runs, ALLOW ports and total
+checked against A's verdicts on the device).
+
 usage: python tools/reach_bench.py [--af 4|16] [--locals 12] [--endpoints 1024,2048]
            [--tiles 1048576,4194304,16777216] [--iters 9] [--kernel-stats]
        python tools/reach_bench.py --diff [--af 4|16] [--diff-locals 12,64] [--endpoints 2048]
            [--iters 9] [--rounds 7]
+       python tools/reach_bench.py --ports [--af 4|16] [--diff-locals 12,64] [--iters 3] [--rounds 5]
+           [--kernel-stats]
 """
 import argparse
 import csv
@@ -269,7 +287,98 @@ def measure_diff(a, n, n_local):
     return line
 
 
-def kernel_stats(a, n, diff_locals=None):
+PORTS_MAX_ROWS = 1 << 32
+
+
+def measure_ports(a, n_local):
+    """A / B of cls_reach_matrix at the class starts and cls_reach_ports."""
+    import torch
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    proto, sport = 0, 40000
+    bind, by_name, ifs, at, addrs, _ = setup(eng, a.af, n_local, 2048)
+    # the classes over all interfaces' ACLs: what 2048 endpoints on every interface bind
+    names = sorted({x for i in np.unique(at) for x in bind[ifs[i]] if x is not None})
+    starts = np.unique(np.concatenate([eng.port_classes(by_name[x], proto) for x in names]))
+    K = len(starts)
+    n = max([m for m in (2048, 1024, 512, 256) if K * m * m <= PORTS_MAX_ROWS] or [256])
+    at, addrs = at[:n], addrs[:n]
+    names_n = sorted({x for i in np.unique(at) for x in bind[ifs[i]] if x is not None})
+    assert names_n == names, "the first N endpoints bind fewer ACLs"
+    ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
+    rows = K * n * n
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    ep_if = np.ascontiguousarray(ids[at], np.uint32)
+    ep_addr = np.ascontiguousarray(addrs, np.uint8 if a.af == 16 else np.uint32)
+    pr, sp = np.full(K, proto, np.uint8), np.full(K, sport, np.uint16)
+    dp = starts.astype(np.uint16)
+    spec_a = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                            _ptr(ep_addr) if a.af == 16 else None, K, _ptr(pr), _ptr(sp), _ptr(dp))
+    spec_b = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                            _ptr(ep_addr) if a.af == 16 else None, 1, _ptr(pr), _ptr(sp), None)
+    dv = torch.empty(rows, dtype=torch.uint8, device="cuda")
+    total = torch.zeros(1, dtype=torch.int64, device="cuda")
+    runs = torch.empty((n, n), dtype=torch.int32, device="cuda")
+    allow = torch.empty((n, n), dtype=torch.int32, device="cuda")
+    hist = torch.empty(4, dtype=torch.int64, device="cuda")
+    k_out = np.zeros(1, np.uint32)
+    # the ranges are counted first: the cap of the timed calls is their total
+    o = _abi.ReachPortsOut(None, 0, _ptr(total), None, None, None, _ptr(k_out))
+    assert L.cls_reach_ports(eng.h, C.byref(spec_b), C.byref(o), _abi.F_DEVICE, None) == 0, L.cls_last_error(eng.h)
+    sync()
+    n_ranges = int(total[0])
+    assert int(k_out[0]) == K, (int(k_out[0]), K)
+    rec = torch.empty((n_ranges, 4), dtype=torch.int32, device="cuda")
+    o = _abi.ReachPortsOut(_ptr(rec), n_ranges, _ptr(total), _ptr(runs), _ptr(allow), _ptr(hist), _ptr(k_out))
+
+    def matrix():
+        rc = L.cls_reach_matrix(eng.h, C.byref(spec_a), _ptr(dv), None, None, _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+
+    def ports():
+        rc = L.cls_reach_ports(eng.h, C.byref(spec_b), C.byref(o), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+    ta, tb = [], []
+    for _ in range(a.rounds):
+        ta.append(piped(matrix, a.iters, sync))
+        tb.append(piped(ports, a.iters, sync))
+    # parity on the device: A's verdicts, [K, N, N], run-length encoded per pair
+    sync()
+    v = dv.view(K, n * n)
+    want_runs = torch.ones(n * n, dtype=torch.int64, device="cuda")
+    width = torch.from_numpy(np.diff(np.append(starts.astype(np.int64), 65536))).to("cuda")
+    want_allow = torch.zeros(n * n, dtype=torch.int64, device="cuda")
+    want_hist = torch.zeros(4, dtype=torch.int64, device="cuda")
+    for k in range(K):
+        if k:
+            want_runs += v[k] != v[k - 1]
+        want_allow += (v[k] == 2) * width[k]
+        want_hist += torch.bincount(v[k].to(torch.int64), minlength=4) * width[k]
+    assert torch.equal(runs.flatten().to(torch.int64), want_runs), "runs differ from the matrix at the class starts"
+    assert torch.equal(allow.flatten().to(torch.int64), want_allow) and torch.equal(hist, want_hist)
+    assert int(total[0]) == n_ranges == int(want_runs.sum())
+    r = rec.to(torch.int64)
+    pair = r[:, 0] * n + r[:, 1]
+    assert bool((pair[1:] >= pair[:-1]).all()) and torch.equal(torch.bincount(pair, minlength=n * n), want_runs)
+    t_a, t_b = float(np.median(ta)), float(np.median(tb))
+    line = {"metric": "port sweep: B / A (cls_reach_ports(CLS_F_DEVICE) with ranges, total, runs, ALLOW ports and "
+                      "histogram against cls_reach_matrix(CLS_F_DEVICE, verdicts) with K probes at the class starts, "
+                      "alternated in one process)",
+            "af": a.af, "endpoints": n, "endpoints_rule": "largest of 2048, 1024, 512, 256 with K N^2 <= 2^32",
+            "K": K, "rows": rows, "local_acls": n_local, "acls_bound": len(names),
+            "options": a.opt, "iters": a.iters, "rounds": a.rounds,
+            "A_ms": round(t_a, 4), "B_ms": round(t_b, 4), "B_over_A": round(t_b / t_a, 4),
+            "A_ms_rounds": [round(x, 4) for x in ta], "B_ms_rounds": [round(x, 4) for x in tb],
+            "ranges": n_ranges, "ranges_per_pair_max": int(want_runs.max()),
+            "A_bytes_out": rows, "B_bytes_out": n_ranges * 16 + 2 * n * n * 4 + 40,
+            "verdict_cells": hist.cpu().numpy().tolist(),
+            "parity": "runs, ALLOW ports, histogram, total and the records' pairs == run-length of A's verdicts"}
+    eng.close()
+    return line
+
+
+def kernel_stats(a, n, diff_locals=None, ports=False):
     """The same measurement in a child under rocprofv3 --kernel-trace --stats
     (a run of its own: the timings above are taken without the profiler):
     average ns per call of the matrix's kernels and of connect_kernel
@@ -278,7 +387,7 @@ def kernel_stats(a, n, diff_locals=None):
     with tempfile.TemporaryDirectory() as d:
         mode = ["--locals", str(a.locals), "--tiles", str(a.stats_tile), "--cpu-sample", "256"]
         if diff_locals is not None:
-            mode = ["--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
+            mode = ["--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--endpoints", str(n),
                "--iters", str(a.iters)] + mode + [x for o in a.opt for x in ("--opt", o)]
@@ -292,7 +401,8 @@ def kernel_stats(a, n, diff_locals=None):
         for row in csv.DictReader(open(files[0])):
             name = row["Name"]
             for key in ("reach_expand4", "reach_expand16", "reach_reduce", "reach_diff_count", "reach_diff_scan",
-                        "reach_diff_emit", "connect_kernel"):
+                        "reach_diff_emit", "reach_ports_expand4", "reach_ports_expand16", "reach_ports_count",
+                        "reach_ports_emit", "connect_kernel"):
                 if key in name:
                     e = out.setdefault(key, {"calls": 0, "total_ns": 0})
                     e["calls"] += int(row["Calls"])
@@ -314,11 +424,34 @@ def main():
     ap.add_argument("--stats-tile", type=int, default=1 << 22, help="the tile size of the --kernel-stats run")
     ap.add_argument("--diff", action="store_true", help="A / B of cls_reach_matrix and cls_reach_diff")
     ap.add_argument("--diff-locals", default="12,64")
-    ap.add_argument("--rounds", type=int, default=7, help="--diff: alternations of A and B")
+    ap.add_argument("--ports", action="store_true", help="A / B of cls_reach_matrix at the class starts and "
+                                                         "cls_reach_ports")
+    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports: alternations of A and B")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     a.tiles = [int(x) for x in a.tiles.split(",")]
+    if a.ports:
+        for n_local in [int(x) for x in a.diff_locals.split(",")]:
+            line = measure_ports(a, n_local)
+            if a.kernel_stats and not a.child:
+                from vpp_amd import _abi
+                ks = kernel_stats(a, line["endpoints"], n_local, ports=True)
+                # per 4 Mi rows: a launch takes a tile, about reach_tile rows (the last one fewer)
+                tile = 16 << 20
+                b_rows = line["rows"] / -(-line["endpoints"] ** 2 // max(1, tile // line["K"]))
+                a_rows = line["rows"] / -(-line["rows"] // tile)
+                for key, e in ks.items():
+                    if isinstance(e, dict) and "avg_us" in e:
+                        per = b_rows if key.startswith("reach_ports") or key == "reach_diff_scan" else \
+                            a_rows if key.startswith("reach_expand") else (a_rows + b_rows) / 2
+                        e["us_per_4Mi_rows"] = round(e["avg_us"] * (4 << 20) / per, 2)
+                line["kernel_stats"] = dict(ks, sources=_abi.source_hash(),
+                                            note="average per launch over the A and B calls, under the profiler; "
+                                                 "per 4 Mi rows from the rows of an average launch (reach_diff_scan: "
+                                                 "one workgroup per launch)")
+            print(json.dumps(line), flush=True)
+        return
     if a.diff:
         for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
             for n_local in [int(x) for x in a.diff_locals.split(",")]:

@@ -57,7 +57,8 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_batch_destroy", "cls_batch_shards", "cls_batch_shard", "cls_batch_field", "cls_batch_mirror",
            "cls_batch_upload", "cls_batch_download", "cls_batch_gen_traffic_v4", "cls_batch_gen_traffic_v16",
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
-           "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff"]
+           "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
+           "cls_port_classes"]
 
 
 class ClsRule(C.Structure):
@@ -100,6 +101,22 @@ class ReachDiffOut(C.Structure):
                 ("changes", C.c_void_p), ("cap", C.c_uint64), ("n_changes", C.c_void_p), ("trans_out", C.c_void_p),
                 ("changed_out", C.c_void_p)]
 
+
+class PortRange(C.Structure):
+    """cls_port_range: one maximal port range of a pair, 16 bytes."""
+    _fields_ = [("src", C.c_uint32), ("dst", C.c_uint32), ("port_lo", C.c_uint16), ("port_hi", C.c_uint16),
+                ("action", C.c_uint8), ("zero", C.c_uint8 * 3)]
+
+
+class ReachPortsOut(C.Structure):
+    """cls_reach_ports_out: the outputs of cls_reach_ports, each optional."""
+    _fields_ = [("ranges", C.c_void_p), ("cap", C.c_uint64), ("n_ranges", C.c_void_p), ("runs_out", C.c_void_p),
+                ("allow_ports_out", C.c_void_p), ("hist_out", C.c_void_p), ("n_classes", C.c_void_p)]
+
+
+# cls_port_range as a numpy structured dtype (16 bytes)
+PORT_RANGE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("port_lo", "<u2"), ("port_hi", "<u2"), ("action", "u1"),
+                       ("zero", "u1", (3,))])
 
 # cls_reach_change as a numpy structured dtype (16 bytes)
 REACH_CHANGE = np.dtype([("probe", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("was", "u1"), ("now", "u1"),
@@ -233,6 +250,8 @@ def bind(path: str, strict: bool = True):
         "cls_conn_counters": (C.c_int, [vp, u32, vp, u32]),
         "cls_reach_matrix": (C.c_int, [vp, C.POINTER(ReachSpec), vp, vp, vp, u32, vp]),
         "cls_reach_diff": (C.c_int, [vp, C.POINTER(ReachSpec), vp, C.POINTER(ReachDiffOut), u32, vp]),
+        "cls_reach_ports": (C.c_int, [vp, C.POINTER(ReachSpec), C.POINTER(ReachPortsOut), u32, vp]),
+        "cls_port_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -148,6 +148,9 @@ struct Table {
     // counters (CLS_F_COUNT; allocated on first use, R + 1 u64)
     std::vector<ConnRule4> conn4;
     std::vector<ConnRule16> conn16;
+    // cls_reach_ports: the table's port class starts for TCP / UDP
+    // (port_class_starts: sorted, unique, the first is 0)
+    std::vector<uint16_t> port_lo[2];
     // the bitmap form of conn4 (conn_bitmap4), built on the first connection
     // batch that wants it; empty when its tables exceed kConnBmMaxWords
     std::vector<uint32_t> conn_bm;
@@ -243,6 +246,10 @@ struct cls_engine {
     // and each chunk's first record index, the call's running total (one
     // u64), the u64 transition and u32 changed-cell accumulators
     DevBuf r_base, r_changes, r_dcount, r_dbase, r_dtotal, r_trans, r_changed;
+    // cls_reach_ports (reach.cpp), under the same rule: the u32 runs and ALLOW
+    // ports per pair of a host call, the u64 histogram (its tiles, records,
+    // chunk counts and total use the matrix's and the diff's buffers)
+    DevBuf r_runs, r_pallow, r_phist;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits
@@ -330,6 +337,11 @@ inline Pkts4 framed(const Cls4Image& im, const Pkts4& p) {
 Fe16 fe16(const Cls16Image& m, const DevBuf& d_src_search);
 int cls_grid(const cls_engine* e, bool use_cls, bool lds_resident, uint32_t lds_bytes, uint64_t n);
 int upload(cls_engine* e, DevBuf& d, const Cls4Image& im);
+
+// reach.cpp (cls_port_classes): the port class starts of a rule list for a
+// protocol (TCP, UDP; anything else: {0}) -- 0, and lo16 and hi16 + 1 <= 65535
+// of the rules that carry a destination range for it; sorted and unique
+std::vector<uint16_t> port_class_starts(const cls_rule* rules, uint32_t n, uint32_t proto);
 
 // ---- engine.cpp / connect.cpp internals used by fleet.cpp (the caller holds e->mu)
 int engine_open(int device, cls_engine** out);

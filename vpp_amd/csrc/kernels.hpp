@@ -433,6 +433,54 @@ hipError_t launch_reach_diff_emit(const ReachTile& t, const uint8_t* base, const
                                   const uint32_t* chunk_count, const unsigned long long* chunk_base, uint4* changes,
                                   unsigned long long cap, uint8_t* store, int n_cu, hipStream_t s);
 
+// ---- the reachability port sweep (k_reach_ports.hip; contivcls.h cls_reach_ports)
+// One tile of the sweep: rows [0, n) are the whole pairs from (s0, d0) on,
+// pair-major -- row i is class i % K of pair i / K after the tile's first,
+// n = pairs x K <= 2^30.  Every index the kernels form is 32-bit; the host
+// passes runs / allow offset to the tile's first pair.  lo: the K class
+// starts (ascending, lo[0] == 0); class k is [lo[k], lo[k + 1] - 1], the last
+// one ends at 65535.
+struct ReachPortsTile {
+    uint32_t n_ep;               // N
+    uint32_t s0, d0;             // the tile's first pair
+    uint32_t K;                  // classes per pair
+    uint32_t n;                  // rows in the tile
+    const uint16_t* lo;
+};
+// The tile's rows as a device batch's arrays, in reach_expand's store shape
+// (four rows per lane, the last group padded by repetition): dport = lo[k],
+// sport and proto constant.
+struct ReachPortsExpand {
+    const uint32_t* ep_if;
+    const void* ep_addr;
+    uint32_t sport, proto;
+    uint32_t *src_if, *dst_if;
+    void *src, *dst;
+    uint16_t *sport_out, *dport_out;
+    uint8_t* proto_out;
+};
+hipError_t launch_reach_ports_expand(const ReachPortsTile& t, const ReachPortsExpand& x, bool k16, int n_cu,
+                                     hipStream_t s);
+// A row starts a range when k == 0 or its verdict byte differs from the row
+// before.  count: chunk_count[chunk] = the starts among the chunk's
+// kReachChunk rows (or null); runs[pair'] += the pair's starts; allow[pair']
+// += width(k) of the rows with CLS_CONN_ALLOW; hist[action] += width(k)
+// (binned in LDS, each non-zero bin added once per chunk); each may be null.
+// verdict: the tile's n bytes, 4-B aligned.
+hipError_t launch_reach_ports_count(const ReachPortsTile& t, const uint8_t* verdict, uint32_t* chunk_count,
+                                    uint32_t* runs, uint32_t* allow, unsigned long long* hist, int n_cu,
+                                    hipStream_t s);
+// emit (behind launch_reach_diff_scan of the chunk counts): the record of the
+// range with index j = chunk_base[chunk] + its start's rank in the chunk
+// (cls_port_range) while j < cap.  The start row writes src, dst, port_lo and
+// the action word; the range's last row -- whose index is the starts up to
+// and including it, less one -- writes port_hi; a range of one row takes one
+// 16-B store.  No range crosses a tile, so every record below min(total,
+// cap) is complete when the launch ends.
+hipError_t launch_reach_ports_emit(const ReachPortsTile& t, const uint8_t* verdict,
+                                   const unsigned long long* chunk_base, uint4* ranges, unsigned long long cap,
+                                   int n_cu, hipStream_t s);
+
 struct TrafficDev {
     uint64_t seed;
     uint32_t pct_pod, pct_dst, pct_port, pct_icmp;

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "../../include/contivcls.h"
@@ -59,16 +60,29 @@ static hipError_t reach_grow(cls_engine* e, DevBuf& d, size_t bytes) {
     return d.ensure(bytes);
 }
 
+// The endpoint arrays of `spec` (the probes' arrays are the caller's to check).
+static int reach_spec(cls_engine* e, const cls_reach_spec* sp, ReachCall& R) {
+    R.k16 = sp->af == CLS_AF_V16;
+    if (!R.k16 && sp->af != CLS_AF_V4) return fail(e, CLS_E_INVAL, "af must be CLS_AF_V4 or CLS_AF_V16");
+    if (!sp->n_endpoints || !sp->n_probes) return fail(e, CLS_E_INVAL, "reach matrix without endpoints or probes");
+    if (!sp->if_id || !(R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4) || !sp->proto || !sp->sport)
+        return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
+    return CLS_OK;
+}
+static int reach_spec_ifs(cls_engine* e, const cls_reach_spec* sp) {
+    const uint32_t n_ifs = uint32_t(e->if_acl.size());
+    for (uint32_t i = 0; i < sp->n_endpoints; ++i)
+        if (sp->if_id[i] >= n_ifs) return fail(e, CLS_E_INVAL, "endpoint %u: unknown interface id", i);
+    return CLS_OK;
+}
+
 // Checks everything a refusal can depend on: no device work is queued before
 // this returns CLS_OK.
 static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdict_out, uint64_t* hist_out,
                         uint32_t* allow_out, uint32_t flags, void* stream, ReachCall& R) {
-    R.k16 = sp->af == CLS_AF_V16;
-    if (!R.k16 && sp->af != CLS_AF_V4) return fail(e, CLS_E_INVAL, "af must be CLS_AF_V4 or CLS_AF_V16");
-    if (!sp->n_endpoints || !sp->n_probes) return fail(e, CLS_E_INVAL, "reach matrix without endpoints or probes");
-    if (!sp->if_id || !(R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4) || !sp->proto || !sp->sport ||
-        !sp->dport)
-        return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
+    int rc = reach_spec(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    if (!sp->dport) return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
     // (a diff has outputs of its own, and its verdict_out may simply be NULL)
     if (!R.base && !verdict_out && !hist_out && !allow_out)
         return fail(e, CLS_E_INVAL, "reach matrix without an output");
@@ -83,9 +97,8 @@ static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdic
     R.dev = flags & CLS_F_DEVICE;
     if (R.dev && (!aligned(verdict_out, 16) || !aligned(hist_out, 8) || !aligned(allow_out, 4)))
         return fail(e, CLS_E_INVAL, "device outputs: verdict_out 16-byte, hist_out 8-byte, allow_out 4-byte aligned");
-    const uint32_t n_ifs = uint32_t(e->if_acl.size());
-    for (uint32_t i = 0; i < R.N; ++i)
-        if (sp->if_id[i] >= n_ifs) return fail(e, CLS_E_INVAL, "endpoint %u: unknown interface id", i);
+    rc = reach_spec_ifs(e, sp);
+    if (rc != CLS_OK) return rc;
     R.mode = flags & (CLS_F_COUNT | CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR);
     R.tile = e->opts.reach_tile;
     R.s = stream ? static_cast<hipStream_t>(stream) : e->stream;
@@ -123,31 +136,36 @@ static int reach_diff_inputs(cls_engine* e, const cls_reach_diff_out* o, ReachCa
     return CLS_OK;
 }
 
-// The endpoint and probe tables, uploaded once per call from the engine's
-// copy (the caller's arrays are not read after this); nothing is copied when
-// the last call's tables are the same.  Orders the call behind the last
+// The call's tables (one blob), uploaded once per call from the engine's copy
+// (the caller's arrays are not read after this); nothing is copied when the
+// last call's blob is the same.  Orders the call behind the last
 // stream-ordered batch of another stream, which may still use the scratch.
-static int reach_upload(cls_engine* e, const cls_reach_spec* sp, const ReachCall& R) {
+static int reach_upload_tab(cls_engine* e, const ReachCall& R, std::vector<uint8_t>& tab) {
     HIPC(e, hipSetDevice(e->device));
     if (e->conn_last && e->conn_last != R.s) {
         if (!e->conn_sync_ev) HIPC(e, hipEventCreateWithFlags(&e->conn_sync_ev, hipEventDisableTiming));
         HIPC(e, hipEventRecord(e->conn_sync_ev, e->conn_last));
         HIPC(e, hipStreamWaitEvent(R.s, e->conn_sync_ev, 0));
     }
+    const void* was = e->r_tab.p;
+    HIPC(e, reach_grow(e, e->r_tab, tab.size()));
+    if (e->r_tab.p == was && e->reach_up == tab) return CLS_OK;
+    const int rc = conn_quiesce(e);                  // an earlier copy may still read reach_up
+    if (rc != CLS_OK) return rc;
+    e->reach_up.swap(tab);
+    HIPC(e, hipMemcpyAsync(e->r_tab.p, e->reach_up.data(), e->reach_up.size(), hipMemcpyHostToDevice, R.s));
+    return CLS_OK;
+}
+
+// The endpoint and probe tables.
+static int reach_upload(cls_engine* e, const cls_reach_spec* sp, const ReachCall& R) {
     std::vector<uint8_t> tab(R.tab_bytes, 0);
     std::memcpy(tab.data(), sp->if_id, size_t(R.N) * 4);
     std::memcpy(tab.data() + R.off_addr, R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4,
                 size_t(R.N) * (R.k16 ? 16 : 4));
     uint2* pr = reinterpret_cast<uint2*>(tab.data() + R.off_probe);
     for (uint32_t p = 0; p < R.P; ++p) pr[p] = uint2{uint32_t(sp->sport[p]) | uint32_t(sp->dport[p]) << 16, sp->proto[p]};
-    const void* was = e->r_tab.p;
-    HIPC(e, reach_grow(e, e->r_tab, R.tab_bytes));
-    if (e->r_tab.p == was && e->reach_up == tab) return CLS_OK;
-    const int rc = conn_quiesce(e);                  // an earlier copy may still read reach_up
-    if (rc != CLS_OK) return rc;
-    e->reach_up.swap(tab);
-    HIPC(e, hipMemcpyAsync(e->r_tab.p, e->reach_up.data(), R.tab_bytes, hipMemcpyHostToDevice, R.s));
-    return CLS_OK;
+    return reach_upload_tab(e, R, tab);
 }
 
 // The tile's arrays (whole groups of four connections), the verdict bytes
@@ -332,5 +350,265 @@ extern "C" int cls_reach_diff(cls_engine* e, const cls_reach_spec* spec, const u
         rc = reach_tile(e, R, first, uint32_t(std::min(R.tile, R.cells - first)));
     if (rc == CLS_OK) rc = reach_diff_outputs(e, R);
     if (rc == CLS_OK) rc = reach_outputs(e, R);
+    return rc;
+}
+
+// ---- cls_reach_ports: per-pair port ranges over all 65,536 ports ----------
+// One representative port per port class (the swept protocol's rule
+// boundaries over the bound ACLs) is exact, since evalACL sees the destination
+// port only in comparisons with those boundaries.  The K N^2 rows are laid
+// out pair-major, row = (s N + d) K + k, in tiles of whole pairs; per tile the
+// expand launch (k_reach_ports.hip), connect_locked unchanged, then count,
+// reach_diff_scan and emit.
+
+std::vector<uint16_t> port_class_starts(const cls_rule* rules, uint32_t n, uint32_t proto) {
+    std::vector<uint16_t> v{0};
+    if (proto > uint32_t(P_UDP)) return v;            // no rule tests the port
+    const bool tcp = proto == uint32_t(P_TCP);
+    for (uint32_t i = 0; i < n; ++i) {
+        const cls_rule& r = rules[i];
+        if (!(r.flags & (tcp ? CLS_R_TCP : CLS_R_UDP)) || !(r.flags & (tcp ? CLS_R_TCP_DST : CLS_R_UDP_DST))) continue;
+        // the uint16() casts of :559
+        const uint16_t lo = uint16_t(tcp ? r.tcp_dst_lo : r.udp_dst_lo), hi = uint16_t(tcp ? r.tcp_dst_hi : r.udp_dst_hi);
+        if (lo > hi) continue;                        // never inside [lo, hi]
+        v.push_back(lo);
+        if (hi != 0xFFFF) v.push_back(uint16_t(hi + 1));
+    }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+
+extern "C" int cls_port_classes(const cls_rule* rules, uint32_t n_rules, uint32_t proto, uint16_t* lo_out,
+                                uint32_t cap, uint32_t* n) {
+    if (!n || (n_rules && !rules)) return CLS_E_INVAL;
+    const std::vector<uint16_t> v = port_class_starts(rules, n_rules, proto);
+    *n = uint32_t(v.size());
+    if (lo_out && cap >= v.size()) std::copy(v.begin(), v.end(), lo_out);
+    return CLS_OK;
+}
+
+// The call's resolved arguments: R holds the matrix's (one probe, cells =
+// K N^2 rows, tile = the rows of a full tile).
+struct PortsCall {
+    ReachCall R;
+    uint32_t K = 0, sport = 0, proto = 0;
+    uint64_t pairs = 0, per_tile = 0;      // N^2; pairs per tile
+    std::vector<uint16_t> lo;              // the K class starts
+    size_t off_lo = 0;                     // in the tables' blob, behind the addresses
+    cls_reach_ports_out o{};
+    uint64_t cap = 0;                      // min(o.cap, K N^2): no index reaches K N^2
+    bool scan() const { return o.ranges || o.n_ranges; }
+};
+
+// The sorted union of the class starts of the tables bound, inbound or
+// outbound, to any interface of the endpoints.
+static void ports_classes(cls_engine* e, const cls_reach_spec* sp, PortsCall& C) {
+    C.lo.assign(1, 0);
+    const uint32_t proto = sp->proto[0];
+    if (proto > uint32_t(P_UDP)) return;
+    std::vector<uint8_t> seen_if(e->if_acl.size(), 0);
+    std::vector<int32_t> tids;
+    for (uint32_t i = 0; i < sp->n_endpoints; ++i) {
+        if (seen_if[sp->if_id[i]]) continue;
+        seen_if[sp->if_id[i]] = 1;
+        tids.push_back(e->if_acl[sp->if_id[i]].first);
+        tids.push_back(e->if_acl[sp->if_id[i]].second);
+    }
+    std::sort(tids.begin(), tids.end());
+    tids.erase(std::unique(tids.begin(), tids.end()), tids.end());
+    for (int32_t tid : tids) {
+        if (tid < 0) continue;
+        const auto it = e->tables.find(uint32_t(tid));
+        if (it == e->tables.end()) continue;
+        const std::vector<uint16_t>& v = it->second->port_lo[proto];
+        C.lo.insert(C.lo.end(), v.begin(), v.end());
+    }
+    std::sort(C.lo.begin(), C.lo.end());
+    C.lo.erase(std::unique(C.lo.begin(), C.lo.end()), C.lo.end());
+}
+
+// Checks everything a refusal can depend on: no device work is queued before
+// this returns CLS_OK.
+static int ports_inputs(cls_engine* e, const cls_reach_spec* sp, const cls_reach_ports_out* o, uint32_t flags,
+                        void* stream, PortsCall& C) {
+    ReachCall& R = C.R;
+    int rc = reach_spec(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    if (sp->n_probes != 1) return fail(e, CLS_E_INVAL, "reach ports takes one probe (proto[0], sport[0])");
+    if (flags & (CLS_F_COUNT | CLS_F_NO_VERDICT))
+        return fail(e, CLS_E_INVAL, "reach ports evaluates representatives: no CLS_F_COUNT, no CLS_F_NO_VERDICT");
+    if (!o->ranges && !o->n_ranges && !o->runs_out && !o->allow_ports_out && !o->hist_out)
+        return fail(e, CLS_E_INVAL, "reach ports without ranges, n_ranges, runs_out, allow_ports_out or hist_out");
+    if (o->ranges && !o->n_ranges) return fail(e, CLS_E_INVAL, "reach ports: ranges without n_ranges");
+    if (o->ranges && !o->cap) return fail(e, CLS_E_INVAL, "reach ports: ranges with cap 0");
+    R.dev = flags & CLS_F_DEVICE;
+    if (R.dev && (!aligned(o->ranges, 16) || !aligned(o->n_ranges, 8) || !aligned(o->hist_out, 8) ||
+                  !aligned(o->runs_out, 4) || !aligned(o->allow_ports_out, 4)))
+        return fail(e, CLS_E_INVAL, "device reach ports: ranges 16-byte, n_ranges, hist_out 8-byte, runs_out, "
+                                    "allow_ports_out 4-byte aligned");
+    R.N = sp->n_endpoints;
+    R.P = 1;
+    if (R.N > (1u << 18)) return fail(e, CLS_E_INVAL, "reach ports above 2^36 rows (N %u)", R.N);
+    rc = reach_spec_ifs(e, sp);
+    if (rc != CLS_OK) return rc;
+    ports_classes(e, sp, C);
+    C.K = uint32_t(C.lo.size());
+    C.pairs = uint64_t(R.N) * R.N;
+    if (C.pairs > kReachMaxCells / C.K)
+        return fail(e, CLS_E_INVAL, "reach ports above 2^36 rows (K %u classes x N %u endpoints squared)", C.K, R.N);
+    R.cells = C.pairs * C.K;
+    // whole pairs per tile (one when K exceeds reach_tile): no range crosses a tile
+    C.per_tile = std::max<uint64_t>(1, e->opts.reach_tile / C.K);
+    R.tile = C.per_tile * C.K;                        // <= max(reach_tile, 65536) <= 2^30
+    R.mode = flags & (CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR);
+    R.s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    C.o = *o;
+    C.sport = sp->sport[0];
+    C.proto = sp->proto[0];
+    C.cap = o->ranges ? std::min(o->cap, R.cells) : 0;
+    R.off_addr = (size_t(R.N) * 4 + 15) & ~size_t(15);
+    C.off_lo = (R.off_addr + size_t(R.N) * (R.k16 ? 16 : 4) + 15) & ~size_t(15);
+    R.tab_bytes = C.off_lo + ((size_t(C.K) * 2 + 15) & ~size_t(15));
+    if (o->n_classes) *o->n_classes = C.K;
+    return CLS_OK;
+}
+
+// The endpoint table with the class starts behind it.
+static int ports_upload(cls_engine* e, const cls_reach_spec* sp, const PortsCall& C) {
+    const ReachCall& R = C.R;
+    std::vector<uint8_t> tab(R.tab_bytes, 0);
+    std::memcpy(tab.data(), sp->if_id, size_t(R.N) * 4);
+    std::memcpy(tab.data() + R.off_addr, R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4,
+                size_t(R.N) * (R.k16 ? 16 : 4));
+    std::memcpy(tab.data() + C.off_lo, C.lo.data(), size_t(C.K) * 2);
+    return reach_upload_tab(e, R, tab);
+}
+
+// Where the per-pair sums and the histogram accumulate: the caller's device
+// memory, or the engine's for a host call.
+static uint32_t* ports_runs(cls_engine* e, const PortsCall& C) {
+    return !C.o.runs_out ? nullptr : C.R.dev ? C.o.runs_out : e->r_runs.as<uint32_t>();
+}
+static uint32_t* ports_allow(cls_engine* e, const PortsCall& C) {
+    return !C.o.allow_ports_out ? nullptr : C.R.dev ? C.o.allow_ports_out : e->r_pallow.as<uint32_t>();
+}
+static unsigned long long* ports_hist(cls_engine* e, const PortsCall& C) {
+    return !C.o.hist_out ? nullptr
+           : C.R.dev     ? reinterpret_cast<unsigned long long*>(C.o.hist_out)
+                         : e->r_phist.as<unsigned long long>();
+}
+
+// Beyond reach_scratch: a host call's records (cap of them) and sums, the
+// tile's chunk counts and first indices, the running total; all cleared.
+static int ports_scratch(cls_engine* e, const PortsCall& C) {
+    const ReachCall& R = C.R;
+    const size_t n = size_t(std::min(R.tile, R.cells)), pb = size_t(C.pairs) * 4;
+    if (!R.dev) {
+        if (C.o.ranges) HIPC(e, reach_grow(e, e->r_changes, size_t(C.cap) * sizeof(cls_port_range)));
+        if (C.o.runs_out) HIPC(e, reach_grow(e, e->r_runs, pb));
+        if (C.o.allow_ports_out) HIPC(e, reach_grow(e, e->r_pallow, pb));
+        if (C.o.hist_out) HIPC(e, reach_grow(e, e->r_phist, 4 * 8));
+    }
+    if (C.scan()) {
+        const size_t chunks = (n + kReachChunk - 1) / kReachChunk;
+        HIPC(e, reach_grow(e, e->r_dcount, chunks * 4));
+        HIPC(e, reach_grow(e, e->r_dbase, chunks * 8));
+        HIPC(e, reach_grow(e, e->r_dtotal, 8));
+        HIPC(e, hipMemsetAsync(e->r_dtotal.p, 0, 8, R.s));
+    }
+    if (uint32_t* p = ports_runs(e, C)) HIPC(e, hipMemsetAsync(p, 0, pb, R.s));
+    if (uint32_t* p = ports_allow(e, C)) HIPC(e, hipMemsetAsync(p, 0, pb, R.s));
+    if (unsigned long long* p = ports_hist(e, C)) HIPC(e, hipMemsetAsync(p, 0, 4 * 8, R.s));
+    return CLS_OK;
+}
+
+// One tile: the np whole pairs from `pair` on.
+static int ports_tile(cls_engine* e, const PortsCall& C, uint64_t pair, uint32_t np) {
+    const ReachCall& R = C.R;
+    const uint8_t* tab = e->r_tab.as<uint8_t>();
+    const uint32_t n = np * C.K;
+    const ReachPortsTile T{R.N, uint32_t(pair / R.N), uint32_t(pair % R.N), C.K, n,
+                           reinterpret_cast<const uint16_t*>(tab + C.off_lo)};
+    ReachPortsExpand X{};
+    X.ep_if = reinterpret_cast<const uint32_t*>(tab);
+    X.ep_addr = tab + R.off_addr;
+    X.sport = C.sport;
+    X.proto = C.proto;
+    X.src_if = e->r_sif.as<uint32_t>(); X.dst_if = e->r_dif.as<uint32_t>();
+    X.src = e->r_src.p; X.dst = e->r_dst.p;
+    X.sport_out = e->r_sport.as<uint16_t>(); X.dport_out = e->r_dport.as<uint16_t>();
+    X.proto_out = e->r_proto.as<uint8_t>();
+    HIPC(e, launch_reach_ports_expand(T, X, R.k16, e->n_cu, R.s));
+    // the evaluator, unchanged: a device batch over the expanded arrays
+    cls_conn_soa c{};
+    c.pkt.af = R.k16 ? CLS_AF_V16 : CLS_AF_V4;
+    if (R.k16) {
+        c.pkt.src16 = e->r_src.as<uint8_t>(); c.pkt.dst16 = e->r_dst.as<uint8_t>();
+    } else {
+        c.pkt.src4 = e->r_src.as<uint32_t>(); c.pkt.dst4 = e->r_dst.as<uint32_t>();
+    }
+    c.pkt.sport = X.sport_out; c.pkt.dport = X.dport_out; c.pkt.proto = X.proto_out;
+    c.src_if = X.src_if; c.dst_if = X.dst_if;
+    const uint8_t* v = e->r_verdict.as<uint8_t>();
+    const int rc = connect_locked(e, &c, n, e->r_verdict.as<uint8_t>(), CLS_F_DEVICE | R.mode, R.s, false);
+    if (rc != CLS_OK) return rc;
+    uint32_t* runs = ports_runs(e, C);
+    uint32_t* allow = ports_allow(e, C);
+    uint32_t* count = C.scan() ? e->r_dcount.as<uint32_t>() : nullptr;
+    HIPC(e, launch_reach_ports_count(T, v, count, runs ? runs + pair : nullptr, allow ? allow + pair : nullptr,
+                                     ports_hist(e, C), e->n_cu, R.s));
+    if (!C.scan()) return CLS_OK;
+    unsigned long long* at = e->r_dbase.as<unsigned long long>();
+    HIPC(e, launch_reach_diff_scan((n + kReachChunk - 1) / kReachChunk, count, at,
+                                   e->r_dtotal.as<unsigned long long>(), R.s));
+    cls_port_range* rec = !C.o.ranges ? nullptr : R.dev ? C.o.ranges : e->r_changes.as<cls_port_range>();
+    HIPC(e, launch_reach_ports_emit(T, v, at, reinterpret_cast<uint4*>(rec), C.cap, e->n_cu, R.s));
+    return CLS_OK;
+}
+
+// A host call's sums, total and records through the engine's buffers (it
+// waits for the total and copies that many records, none past them); a device
+// call's total.  A device call is stream-ordered (conn_last).
+static int ports_outputs(cls_engine* e, const PortsCall& C) {
+    const ReachCall& R = C.R;
+    if (R.dev) {
+        if (C.o.n_ranges) HIPC(e, hipMemcpyAsync(C.o.n_ranges, e->r_dtotal.p, 8, hipMemcpyDeviceToDevice, R.s));
+        e->conn_last = R.s;
+        return CLS_OK;
+    }
+    const hipMemcpyKind kind = hipMemcpyDeviceToHost;
+    const size_t pb = size_t(C.pairs) * 4;
+    if (C.o.runs_out) HIPC(e, hipMemcpyAsync(C.o.runs_out, e->r_runs.p, pb, kind, R.s));
+    if (C.o.allow_ports_out) HIPC(e, hipMemcpyAsync(C.o.allow_ports_out, e->r_pallow.p, pb, kind, R.s));
+    if (C.o.hist_out) HIPC(e, hipMemcpyAsync(C.o.hist_out, e->r_phist.p, 4 * 8, kind, R.s));
+    uint64_t total = 0;
+    if (C.o.n_ranges) HIPC(e, hipMemcpyAsync(&total, e->r_dtotal.p, 8, kind, R.s));
+    HIPC(e, hipStreamSynchronize(R.s));
+    const uint64_t n = std::min(total, C.cap);
+    if (C.o.ranges && n) {
+        HIPC(e, hipMemcpyAsync(C.o.ranges, e->r_changes.p, size_t(n) * sizeof(cls_port_range), kind, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+    }
+    if (C.o.n_ranges) *C.o.n_ranges = total;
+    e->conn_last = nullptr;
+    return CLS_OK;
+}
+
+extern "C" int cls_reach_ports(cls_engine* e, const cls_reach_spec* spec, const cls_reach_ports_out* out,
+                               uint32_t flags, void* stream) {
+    if (!e || !spec) return CLS_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    if (!out) return fail(e, CLS_E_INVAL, "reach ports without outputs");
+    PortsCall C;
+    int rc = ports_inputs(e, spec, out, flags, stream, C);
+    if (rc != CLS_OK) return rc;
+    rc = ports_upload(e, spec, C);
+    if (rc == CLS_OK) rc = reach_scratch(e, C.R);
+    if (rc == CLS_OK) rc = ports_scratch(e, C);
+    for (uint64_t pair = 0; rc == CLS_OK && pair < C.pairs; pair += C.per_tile)
+        rc = ports_tile(e, C, pair, uint32_t(std::min(C.per_tile, C.pairs - pair)));
+    if (rc == CLS_OK) rc = ports_outputs(e, C);
     return rc;
 }

@@ -34,6 +34,8 @@ TCP, UDP, ICMP = 0, 1, 2
 
 # Engine.reach_diff's result; what was not asked for is None
 ReachDiff = collections.namedtuple("ReachDiff", "verdicts changes n_changes trans changed hist allow")
+# Engine.reach_ports's result
+ReachPorts = collections.namedtuple("ReachPorts", "ranges n_ranges runs allow_ports hist n_classes")
 
 
 def _is_torch(x) -> bool:
@@ -676,6 +678,96 @@ class Engine:
                 res[1] = res[1][:min(res[2], cap)]
         return ReachDiff(*res)
 
+    @staticmethod
+    def port_classes(rules, proto: int) -> np.ndarray:
+        """The port class starts of one rule list for ``proto``
+        (cls_port_classes; no device): ascending u16, the first 0 -- 0 and
+        the lo16 / hi16 + 1 of the rules that test the destination port."""
+        cr = rules if isinstance(rules, _abi.CRules) else _abi.CRules(rules)
+        n = C.c_uint32(0)
+        rc = _abi.lib().cls_port_classes(cr.ptr(), cr.n, proto, None, 0, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_port_classes: rc=%d" % rc)
+        lo = np.zeros(n.value, np.uint16)
+        rc = _abi.lib().cls_port_classes(cr.ptr(), cr.n, proto, _ptr(lo), n.value, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_port_classes: rc=%d" % rc)
+        return lo
+
+    def reach_ports(self, if_ids, addrs, proto: int, sport: int, cap=None, mode: str = "auto", out=None,
+                    stream=None):
+        """The port sweep (cls_reach_ports): on which destination ports, of
+        all 65,536, endpoint s reaches endpoint d -- ``if_ids`` and ``addrs``
+        as reach_matrix, one ``proto`` and ``sport``.  Returns
+        ReachPorts(ranges: the maximal (src, dst, port_lo, port_hi, action)
+        ranges in (src, dst, port_lo) order, n_ranges: all of them, also
+        beyond ``cap``, runs [N, N] u32: ranges per pair, allow_ports [N, N]
+        u32: dports with CONN_ALLOW, hist [4] u64: (pair, dport) cells per
+        ConnectionAction, n_classes: the port classes K evaluated per pair).
+        out None: the host form -- numpy results, ranges a structured array
+        (_abi.PORT_RANGE) cut to min(n_ranges, cap), n_ranges an int; cap None
+        keeps all ranges (a first call counts them), cap 0 asks for none.
+        out a sequence (ranges, n_ranges, runs, allow_ports, hist) of
+        contiguous torch GPU tensors (None allocates one): the device form --
+        ranges an int32 [cap, 4] tensor of (src, dst, port_lo | port_hi << 16,
+        action) rows of which the first min(n_ranges, cap) are written (cap
+        None: its rows), n_ranges int64 [1]; the call only enqueues on
+        ``stream`` (default: the engine's).  n_classes is an int either way."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        ids = np.ascontiguousarray(if_ids, np.uint32)
+        a = np.asarray(addrs)
+        v16 = a.ndim == 2
+        a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+        n = len(ids)
+        if len(a) != n:
+            raise ClsError("reach ports: N interface ids and addresses")
+        pr, sp = np.array([proto], np.uint8), np.array([sport], np.uint16)
+        spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                              _ptr(a) if v16 else None, 1, _ptr(pr), _ptr(sp), None)
+        k = np.zeros(1, np.uint32)
+        fn = _abi.lib().cls_reach_ports
+        if out is None:
+            total = np.zeros(1, np.uint64)
+            if cap is None:
+                o = _abi.ReachPortsOut(None, 0, _ptr(total), None, None, None, _ptr(k))
+                self._check(fn(self.h, C.byref(spec), C.byref(o), flags, None))
+                cap = int(total[0])
+            cap = int(cap)
+            rec = np.zeros(cap, _abi.PORT_RANGE) if cap > 0 else None
+            runs, allow = np.zeros((n, n), np.uint32), np.zeros((n, n), np.uint32)
+            hist = np.zeros(4, np.uint64)
+            o = _abi.ReachPortsOut(_ptr(rec), cap, _ptr(total), _ptr(runs), _ptr(allow), _ptr(hist), _ptr(k))
+            self._check(fn(self.h, C.byref(spec), C.byref(o), flags, None))
+            if rec is not None:
+                rec = rec[:min(int(total[0]), cap)]
+            return ReachPorts(rec, int(total[0]), runs, allow, hist, int(k[0]))
+        import torch
+        res = list(out)
+        if len(res) != 5:
+            raise ClsError("reach ports: out is (ranges, n_ranges, runs, allow_ports, hist)")
+        if cap is None:
+            if res[0] is None:
+                raise ClsError("reach ports: the device form needs cap or a ranges tensor")
+            cap = res[0].shape[0]
+        cap = int(cap)
+        shapes = ((cap, 4), (1,), (n, n), (n, n), (4,))
+        kinds = ((torch.int32, 4), (torch.int64, 8), (torch.int32, 4), (torch.int32, 4), (torch.int64, 8))
+        for i, (sh, (dt, sz)) in enumerate(zip(shapes, kinds)):
+            if i == 0 and cap == 0:
+                res[0] = None
+            elif res[i] is None:
+                res[i] = torch.empty(sh, dtype=dt, device="cuda")
+            elif not (_is_torch(res[i]) and res[i].is_cuda and res[i].is_contiguous() and
+                      res[i].element_size() == sz and tuple(res[i].shape) == sh):
+                raise ClsError("reach ports: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte elements"
+                               % (i, sh, sz))
+        s = None
+        if stream is not None:
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.ReachPortsOut(_ptr(res[0]), cap, _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), _ptr(res[4]), _ptr(k))
+        self._check(fn(self.h, C.byref(spec), C.byref(o), flags | _abi.F_DEVICE, s))
+        return ReachPorts(*res, int(k[0]))
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -1060,6 +1152,34 @@ class ACLEngine:
         at = np.array([e[0] for e in eps])
         out[:, at[:, None], at[None, :]] = v
         return out
+
+    def connection_ports(self, pods, protocol, src_port):
+        """On which destination ports pod s reaches pod d: (ranges, runs),
+        ranges the maximal (src, dst, port_lo, port_hi, action) tuples -- src
+        and dst indices into ``pods`` -- in (src, dst, port_lo) order, such
+        that connection_pod_to_pod(pods[src], pods[dst], protocol, src_port,
+        port) == action for every port of the range, and runs the
+        [len(pods), len(pods)] number of ranges per pair.  One engine call
+        (Engine.reach_ports) over the resolvable endpoints; the pairs of a
+        pod the reference fails before testConnection (connection_matrix) are
+        the one range 0..65535 of CONN_FAILURE."""
+        n = len(pods)
+        runs = np.ones((n, n), np.uint32)
+        eps = self._matrix_endpoints(pods)
+        per = {}                                    # (src, dst) -> its ranges
+        if eps:
+            r = self.engine.reach_ports([e[1] for e in eps], self._matrix_addrs(eps), protocol, src_port)
+            at = np.array([e[0] for e in eps])
+            runs[at[:, None], at[None, :]] = r.runs
+            for c in r.ranges:
+                per.setdefault((int(at[c["src"]]), int(at[c["dst"]])), []).append(
+                    (int(c["port_lo"]), int(c["port_hi"]), int(c["action"])))
+        ranges = []
+        for s in range(n):
+            for d in range(n):
+                for lo, hi, act in per.get((s, d), [(0, 65535, CONN_FAILURE)]):
+                    ranges.append((s, d, lo, hi, act))
+        return ranges, runs
 
     def connection_matrix_diff(self, pods, probes, base, count: bool = False):
         """connection_matrix against a baseline: (matrix, changes), matrix
