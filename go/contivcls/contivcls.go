@@ -996,6 +996,118 @@ func (en *Engine) ReachPorts(pods []podmodel.ID, protocol aclengine.ProtocolType
 	return out, runs, nil
 }
 
+// HopsNone is the hop count of a pod that is not reached (CLS_HOPS_NONE).
+const HopsNone = 255
+
+// Hops is the result of ReachHops over N pods: Hops[s*N+d] is the least number
+// of connections, each allowed under some probe, that lead from pods[s] to
+// pods[d] through other pods of the list -- 0 for s == d, HopsNone when there
+// is no such path within the hop limit; Reach[s] the pods s reaches (its blast
+// radius), Exposed[d] the pods that reach d, Levels[h] the pairs h hops apart.
+type Hops struct {
+	N       int
+	Hops    []uint8
+	Reach   []uint32
+	Exposed []uint32
+	Levels  [256]uint64
+}
+
+// ReachHops answers "if pod s is compromised, what can it reach in any number
+// of hops?" in one engine call (cls_reach_hops): the matrix of ReachMatrix's
+// arguments is evaluated on the device, folded into an adjacency bitmap there
+// and searched from every pod at once; only the hop counts come back.  maxHops
+// bounds the paths (0: 254).  Pods that ConnectionPodToPod fails before
+// testConnection stay out of the call: they reach nothing and nothing reaches
+// them.
+func (en *Engine) ReachHops(pods []podmodel.ID, probes []Probe, maxHops int) (*Hops, error) {
+	en.Lock()
+	defer en.Unlock()
+	N, P := len(pods), len(probes)
+	if maxHops < 0 || maxHops > 254 {
+		return nil, errors.New("ReachHops: maxHops must be 0 .. 254")
+	}
+	out := &Hops{N: N, Hops: make([]uint8, N*N), Reach: make([]uint32, N), Exposed: make([]uint32, N)}
+	for i := range out.Hops {
+		out.Hops[i] = HopsNone
+	}
+	for s := 0; s < N; s++ {
+		out.Hops[s*N+s] = 0
+	}
+	out.Levels[0] = uint64(N)
+	out.Levels[HopsNone] = uint64(N)*uint64(N) - uint64(N)
+	var strs cstrs
+	defer strs.free()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil {
+			continue
+		}
+		ifName, ok := en.podIf(pod, cfg)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	if n == 0 || P == 0 {
+		return out, nil
+	}
+	proto, sport, dport := make([]uint8, P), make([]uint16, P), make([]uint16, P)
+	for p, q := range probes {
+		proto[p], sport[p], dport[p] = uint8(q.Protocol), q.SrcPort, q.DstPort
+	}
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds both structs on the C stack
+	hops, reach, exposed, levels := make([]uint8, n*n), make([]uint32, n), make([]uint32, n), make([]uint64, 256)
+	var rc C.int
+	if v4 {
+		a4 := make([]uint32, n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To4()
+			a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+		}
+		rc = C.clsg_reach_hops_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+			(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+			C.uint32_t(maxHops), (*C.uint8_t)(&hops[0]), (*C.uint32_t)(&reach[0]), (*C.uint32_t)(&exposed[0]),
+			(*C.uint64_t)(&levels[0]), nil, 0)
+	} else {
+		a16 := make([]byte, 16*n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To16()
+			if a == nil {
+				return nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+			}
+			copy(a16[16*k:], a)
+		}
+		rc = C.clsg_reach_hops_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+			(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+			C.uint32_t(maxHops), (*C.uint8_t)(&hops[0]), (*C.uint32_t)(&reach[0]), (*C.uint32_t)(&exposed[0]),
+			(*C.uint64_t)(&levels[0]), nil, 0)
+	}
+	if rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	for s := 0; s < n; s++ {
+		out.Reach[at[s]], out.Exposed[at[s]] = reach[s], exposed[s]
+		for d := 0; d < n; d++ {
+			out.Hops[at[s]*N+at[d]] = hops[s*n+d]
+		}
+	}
+	// the pods left out: N*N - n*n more pairs, all unreached but their diagonal
+	for h := 1; h < HopsNone; h++ {
+		out.Levels[h] = levels[h]
+	}
+	out.Levels[HopsNone] = levels[HopsNone] + uint64(N)*uint64(N) - uint64(n)*uint64(n) - uint64(N-n)
+	return out, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

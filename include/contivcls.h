@@ -49,7 +49,9 @@ extern "C" {
  *    reachability matrix against a baseline: cls_reach_change,
  *    cls_reach_diff_out); cls_reach_ports (per-pair port ranges over all
  *    65,536 destination ports: cls_port_range, cls_reach_ports_out) and
- *    cls_port_classes. */
+ *    cls_port_classes; cls_reach_hops (the multi-hop closure of the matrix:
+ *    hop counts, blast radius, exposure: cls_reach_hops_out, CLS_HOPS_NONE)
+ *    and the hops_rows option. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -194,7 +196,7 @@ int cls_abi_version(void);
  * conn_pre_narrow, pair_qcap, pair_lq, pair_other_global, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
- * up to a multiple of 1024 --, debug_modes, debug_conn, debug_floor) for
+ * up to a multiple of 1024 --, hops_rows, debug_modes, debug_conn, debug_floor) for
  * later calls; every one keeps verdicts and counters exact.  The library never reads the environment:
  * an engine runs its defaults unless told otherwise here.  CLS_E_INVAL for
  * an unknown key or a malformed value. */
@@ -544,6 +546,61 @@ int cls_reach_ports(cls_engine* e, const cls_reach_spec* spec, const cls_reach_p
  * set.  cls_reach_ports uses the sorted union over the bound ACLs. */
 int cls_port_classes(const cls_rule* rules, uint32_t n_rules, uint32_t proto,
                      uint16_t* lo_out, uint32_t cap, uint32_t* n);
+
+/* ---- reachability hops: multi-hop closure and blast radius of the matrix ---
+ * "If endpoint s is compromised, what can it reach in any number of hops, and
+ * how many hops away is each endpoint?"  The graph: the N endpoints, with an
+ * edge s -> d (s != d) iff the cell byte of (p, s, d) equals CLS_CONN_ALLOW
+ * for at least one probe p (the union over probes; a per-probe answer is a
+ * call with one probe).  Any other byte is no edge, and the diagonal is
+ * ignored.  hops[s][d] is the length of a shortest path if it is at most H,
+ * else CLS_HOPS_NONE; hops[s][s] == 0.  H is max_hops, 0 meaning 254.  Every
+ * output (cls_reach_hops_out), each optional but not all NULL, is a function
+ * of hops alone, so independent of reach_tile, the evaluator, hops_rows and
+ * the scheduling:
+ *   hops_out    [N][N]  the hop counts
+ *   reach_out   [N]     per source the destinations d != s with hops <= H
+ *                       (its blast radius)
+ *   exposed_out [N]     per destination the sources s != d that reach it
+ *   level_out   [256]   pairs (s, d) per hops value; [0] == N, [255] the
+ *                       unreached
+ *   closure_out [N][W]  W = (N + 63) / 64: bit (d & 63) of word d >> 6 of row
+ *                       s is set iff hops[s][d] != CLS_HOPS_NONE; the padding
+ *                       bits are zero
+ * matrix == NULL: the matrix of `spec` is evaluated exactly as
+ * cls_reach_matrix does (bindings snapshotted once, the same tiles,
+ * CLS_F_CONN_CLS / CLS_F_FORCE_LINEAR / CLS_F_COUNT as there: the whole matrix
+ * is evaluated), but its P N^2 verdict bytes never leave the tile scratch:
+ * each tile's ALLOW cells are folded into an engine-owned bitmap of N W
+ * words.  matrix != NULL: a [P][N][N] matrix of an earlier call -- device
+ * memory, 16-byte aligned, with CLS_F_DEVICE, else host memory, which goes
+ * up tile by tile through engine-owned scratch (no caller pointer is kept) --
+ * is folded instead and no ACL is evaluated: only n_endpoints and n_probes of
+ * `spec` are read (the arrays may be NULL), and the evaluator flags and
+ * CLS_F_COUNT are refused.  Flags: CLS_F_DEVICE -- the outputs are device
+ * memory (hops_out 16-byte, level_out and closure_out 8-byte, reach_out and
+ * exposed_out 4-byte aligned) and the call only enqueues on `stream`, ordered
+ * like a device connection batch; without it they are host arrays, filled
+ * through engine-owned buffers.  CLS_E_INVAL, before any device work and with
+ * the outputs untouched: everything cls_reach_matrix refuses of `spec` (with
+ * a matrix only N or P zero and the cell bound), `out` NULL, no output,
+ * CLS_F_NO_VERDICT, a misaligned device pointer, max_hops > 254, N > 32,768
+ * (N in cls_last_error; a bit row is then at most 4 KiB, so that a
+ * workgroup's rows fit LDS, and hops_out at most 1 GiB).  The hops_rows
+ * option (cls_engine_set_option): the source rows a workgroup of the search
+ * owns, 4, 8 or 16 (0, the default: 4).  On a multi-device engine the call
+ * runs on the first device. */
+#define CLS_HOPS_NONE 255u   /* not reached within max_hops */
+
+typedef struct cls_reach_hops_out {
+    uint8_t* hops_out;
+    uint32_t* reach_out;
+    uint32_t* exposed_out;
+    uint64_t* level_out;
+    uint64_t* closure_out;
+} cls_reach_hops_out;
+int cls_reach_hops(cls_engine* e, const cls_reach_spec* spec, const uint8_t* matrix,
+                   uint32_t max_hops, const cls_reach_hops_out* out, uint32_t flags, void* stream);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

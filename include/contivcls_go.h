@@ -314,6 +314,60 @@ static inline int clsg_reach_ports_v16(cls_engine* e, const uint32_t* if_id, con
     return cls_reach_ports(e, &r, &o, flags, NULL);
 }
 
+/* cls_reach_hops over IPv4 endpoints: the multi-hop closure of the matrix of
+ * clsg_reach_matrix_v4's arguments, evaluated on the device and never stored,
+ * paths of at most max_hops edges (0: 254).  Host arrays; hops (n x n bytes),
+ * reach and exposed (n each), level (256) and closure (n x (n + 63) / 64) may
+ * each be NULL, but not all. */
+static inline int clsg_reach_hops_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                     const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                     uint32_t n_probes, uint32_t max_hops, uint8_t* hops, uint32_t* reach,
+                                     uint32_t* exposed, uint64_t* level, uint64_t* closure, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_hops_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.hops_out = hops;
+    o.reach_out = reach;
+    o.exposed_out = exposed;
+    o.level_out = level;
+    o.closure_out = closure;
+    return cls_reach_hops(e, &r, NULL, max_hops, &o, flags, NULL);
+}
+
+/* cls_reach_hops over 16-byte endpoints (n x 16 network-order bytes). */
+static inline int clsg_reach_hops_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                      const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                      uint32_t n_probes, uint32_t max_hops, uint8_t* hops, uint32_t* reach,
+                                      uint32_t* exposed, uint64_t* level, uint64_t* closure, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_hops_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.hops_out = hops;
+    o.reach_out = reach;
+    o.exposed_out = exposed;
+    o.level_out = level;
+    o.closure_out = closure;
+    return cls_reach_hops(e, &r, NULL, max_hops, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

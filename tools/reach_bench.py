@@ -52,12 +52,32 @@ and prints one JSON line: the median ms per call of A and B, B / A, K, the
 ranges and the bytes each leaves to download (B's runs, ALLOW ports and total
 checked against A's verdicts on the device).
 
+--hops measures the hop closure (cls_reach_hops) instead: per --locals value
+of --diff-locals, N = 2048 endpoints (--endpoints) x 4 probes, in one process
+it alternates
+
+  A  cls_reach_matrix(CLS_F_DEVICE) with verdicts, histogram and allow counts:
+     what a caller can do on the device without the call -- the P N^2 verdicts
+     are still to be downloaded and searched on the host;
+  B  cls_reach_hops(CLS_F_DEVICE) over the same spec with the hop counts, the
+     reach counts and the level histogram;
+
+and prints one JSON line per --locals value: the median ms per call of A and
+B, B / A, B at every block height (hops_rows 4, 8, 16), once and labelled as
+CPU the host alternative (downloading A's verdicts and running the tests'
+numpy search, reach_hops_cases.hops_ref, on them; B's hop counts are checked
+against it), and a last line for the matrix form at N = 8192 on a synthetic
+random device matrix of out-degree about 2 (checked against a queue search
+from 64 sources).
+
 usage: python tools/reach_bench.py [--af 4|16] [--locals 12] [--endpoints 1024,2048]
            [--tiles 1048576,4194304,16777216] [--iters 9] [--kernel-stats]
        python tools/reach_bench.py --diff [--af 4|16] [--diff-locals 12,64] [--endpoints 2048]
            [--iters 9] [--rounds 7]
        python tools/reach_bench.py --ports [--af 4|16] [--diff-locals 12,64] [--iters 3] [--rounds 5]
            [--kernel-stats]
+       python tools/reach_bench.py --hops [--af 4|16] [--diff-locals 12,64] [--endpoints 2048] [--iters 9]
+           [--rounds 7] [--kernel-stats]
 """
 import argparse
 import csv
@@ -378,7 +398,142 @@ def measure_ports(a, n_local):
     return line
 
 
-def kernel_stats(a, n, diff_locals=None, ports=False):
+HOPS_SYNTH_N = 8192
+
+
+def measure_hops(a, n, n_local):
+    """A / B of cls_reach_matrix and cls_reach_hops on the same engine."""
+    import torch
+    import reach_hops_cases as hc
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    bind, by_name, ifs, at, addrs, (pr, sp, dp) = setup(eng, a.af, n_local, n)
+    ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
+    cells = N_PROBES * n * n
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    ep_if = np.ascontiguousarray(ids[at], np.uint32)
+    ep_addr = np.ascontiguousarray(addrs, np.uint8 if a.af == 16 else np.uint32)
+    spec = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                          _ptr(ep_addr) if a.af == 16 else None, N_PROBES, _ptr(pr), _ptr(sp), _ptr(dp))
+    dv = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    dh = torch.empty((N_PROBES, 4), dtype=torch.int64, device="cuda")
+    da = torch.empty((N_PROBES, n), dtype=torch.int32, device="cuda")
+    hops = torch.empty((n, n), dtype=torch.uint8, device="cuda")
+    reach = torch.empty(n, dtype=torch.int32, device="cuda")
+    levels = torch.empty(256, dtype=torch.int64, device="cuda")
+    out = _abi.ReachHopsOut(_ptr(hops), _ptr(reach), None, _ptr(levels), None)
+
+    def matrix():
+        rc = L.cls_reach_matrix(eng.h, C.byref(spec), _ptr(dv), _ptr(dh), _ptr(da), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+
+    def closure():
+        rc = L.cls_reach_hops(eng.h, C.byref(spec), None, 0, C.byref(out), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+    ta, tb = [], []
+    for _ in range(a.rounds):
+        ta.append(piped(matrix, a.iters, sync))
+        tb.append(piped(closure, a.iters, sync))
+    by_rows = {}
+    if not a.child:
+        for rows in (4, 8, 16):
+            eng.set_option("hops_rows", rows)
+            by_rows[str(rows)] = round(float(np.median([piped(closure, a.iters, sync) for _ in range(3)])), 4)
+        eng.set_option("hops_rows", None)
+    # the host alternative, once: A's verdicts downloaded and searched on the CPU; B checked against it
+    closure()
+    sync()
+    line = {"metric": "hop closure: B / A (cls_reach_hops(CLS_F_DEVICE) with hop counts, reach counts and the level "
+                      "histogram against cls_reach_matrix(CLS_F_DEVICE) with verdicts, histogram and allow counts "
+                      "over the same spec, alternated in one process)",
+            "af": a.af, "endpoints": n, "probes": N_PROBES, "cells": cells, "local_acls": n_local,
+            "options": a.opt, "iters": a.iters, "rounds": a.rounds}
+    t_a, t_b = float(np.median(ta)), float(np.median(tb))
+    line.update({"A_ms": round(t_a, 4), "B_ms": round(t_b, 4), "B_over_A": round(t_b / t_a, 4),
+                 "A_ms_rounds": [round(x, 4) for x in ta], "B_ms_rounds": [round(x, 4) for x in tb],
+                 "B_ms_by_hops_rows": by_rows})
+    if not a.child:
+        t0 = time.perf_counter()
+        v = dv.cpu().numpy().reshape(N_PROBES, n, n)
+        t1 = time.perf_counter()
+        want = hc.hops_ref(hc.adjacency(v))
+        t2 = time.perf_counter()
+        got = hops.cpu().numpy()
+        assert np.array_equal(got, want), "cls_reach_hops differs from hops_ref of cls_reach_matrix's verdicts"
+        w_reach, _, w_levels, _ = hc.sums(want)
+        assert np.array_equal(reach.cpu().numpy().view(np.uint32), w_reach)
+        assert np.array_equal(levels.cpu().numpy().view(np.uint64), w_levels)
+        line.update({"CPU_download_ms": round((t1 - t0) * 1e3, 2), "CPU_hops_ref_ms": round((t2 - t1) * 1e3, 2),
+                     "CPU_note": "the host alternative, measured once on the CPU: A's %d verdict bytes downloaded, "
+                                 "then the numpy level-synchronous search" % cells,
+                     "levels": {str(k): int(c) for k, c in enumerate(w_levels) if c},
+                     "A_bytes_out": cells, "B_bytes_out": n * n + n * 4 + 256 * 8,
+                     "parity": "hop counts, reach counts and levels == hops_ref / sums of A's verdicts"})
+    eng.close()
+    return line
+
+
+def measure_hops_matrix(a):
+    """The matrix form at N = 8192 on a synthetic random device matrix."""
+    import torch
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr
+    n = HOPS_SYNTH_N
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    g = torch.Generator(device="cuda")
+    g.manual_seed(5)
+    m = torch.where(torch.rand((n, n), device="cuda", generator=g) < 2.0 / n, 2, 0).to(torch.uint8).contiguous()
+    spec = _abi.ReachSpec(_abi.AF_V4, n, None, None, None, 1, None, None, None)
+    hops = torch.empty((n, n), dtype=torch.uint8, device="cuda")
+    reach = torch.empty(n, dtype=torch.int32, device="cuda")
+    levels = torch.empty(256, dtype=torch.int64, device="cuda")
+    out = _abi.ReachHopsOut(_ptr(hops), _ptr(reach), None, _ptr(levels), None)
+
+    def closure():
+        rc = L.cls_reach_hops(eng.h, C.byref(spec), _ptr(m), 0, C.byref(out), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+    t = [piped(closure, 3, sync) for _ in range(3)]
+    by_rows = {}
+    for rows in (4, 8, 16):
+        eng.set_option("hops_rows", rows)
+        by_rows[str(rows)] = round(float(np.median([piped(closure, 3, sync) for _ in range(3)])), 4)
+    eng.set_option("hops_rows", None)
+    closure()
+    sync()
+    # parity: a queue search from 64 sources over the adjacency lists
+    adj = (m == 2).cpu().numpy()
+    np.fill_diagonal(adj, False)
+    nbr = [np.flatnonzero(r) for r in adj]
+    got = hops.cpu().numpy()
+    for s in np.random.default_rng(3).choice(n, 64, replace=False):
+        dist = np.full(n, 255, np.int64)
+        dist[s] = 0
+        front = [int(s)]
+        for level in range(1, 255):
+            nxt = []
+            for u in front:
+                for v in nbr[u]:
+                    if dist[v] == 255:
+                        dist[v] = level
+                        nxt.append(int(v))
+            front = nxt
+            if not front:
+                break
+        assert np.array_equal(got[s], dist.astype(np.uint8)), "source %d differs from the queue search" % s
+    lv = levels.cpu().numpy()
+    assert int(lv[0]) == n and int(lv.sum()) == n * n
+    line = {"metric": "hop closure, matrix form: cls_reach_hops(CLS_F_DEVICE) over a synthetic random [1, N, N] device "
+                      "matrix of out-degree about 2, with hop counts, reach counts and the level histogram",
+            "endpoints": n, "edges": int(adj.sum()), "options": a.opt, "ms": round(float(np.median(t)), 4),
+            "ms_rounds": [round(x, 4) for x in t], "ms_by_hops_rows": by_rows, "deepest_level": int(np.flatnonzero(lv[:255]).max()),
+            "unreached_pairs": int(lv[255]), "parity": "64 sources == a queue search on the host"}
+    eng.close()
+    return line
+
+
+def kernel_stats(a, n, diff_locals=None, ports=False, hops=False):
     """The same measurement in a child under rocprofv3 --kernel-trace --stats
     (a run of its own: the timings above are taken without the profiler):
     average ns per call of the matrix's kernels and of connect_kernel
@@ -387,7 +542,7 @@ def kernel_stats(a, n, diff_locals=None, ports=False):
     with tempfile.TemporaryDirectory() as d:
         mode = ["--locals", str(a.locals), "--tiles", str(a.stats_tile), "--cpu-sample", "256"]
         if diff_locals is not None:
-            mode = ["--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
+            mode = ["--hops" if hops else "--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--endpoints", str(n),
                "--iters", str(a.iters)] + mode + [x for o in a.opt for x in ("--opt", o)]
@@ -402,7 +557,7 @@ def kernel_stats(a, n, diff_locals=None, ports=False):
             name = row["Name"]
             for key in ("reach_expand4", "reach_expand16", "reach_reduce", "reach_diff_count", "reach_diff_scan",
                         "reach_diff_emit", "reach_ports_expand4", "reach_ports_expand16", "reach_ports_count",
-                        "reach_ports_emit", "connect_kernel"):
+                        "reach_ports_emit", "reach_adj_fold", "reach_hops_bfs", "connect_kernel"):
                 if key in name:
                     e = out.setdefault(key, {"calls": 0, "total_ns": 0})
                     e["calls"] += int(row["Calls"])
@@ -426,11 +581,24 @@ def main():
     ap.add_argument("--diff-locals", default="12,64")
     ap.add_argument("--ports", action="store_true", help="A / B of cls_reach_matrix at the class starts and "
                                                          "cls_reach_ports")
-    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports: alternations of A and B")
+    ap.add_argument("--hops", action="store_true", help="A / B of cls_reach_matrix and cls_reach_hops")
+    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports, --hops: alternations of A and B")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     a.tiles = [int(x) for x in a.tiles.split(",")]
+    if a.hops:
+        for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
+            for n_local in [int(x) for x in a.diff_locals.split(",")]:
+                line = measure_hops(a, n, n_local)
+                if a.kernel_stats and not a.child:
+                    from vpp_amd import _abi
+                    line["kernel_stats"] = dict(kernel_stats(a, n, n_local, hops=True), sources=_abi.source_hash(),
+                                                note="average per launch over the A and B calls, under the profiler")
+                print(json.dumps(line), flush=True)
+        if not a.child:
+            print(json.dumps(measure_hops_matrix(a)), flush=True)
+        return
     if a.ports:
         for n_local in [int(x) for x in a.diff_locals.split(",")]:
             line = measure_ports(a, n_local)

@@ -58,7 +58,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_batch_upload", "cls_batch_download", "cls_batch_gen_traffic_v4", "cls_batch_gen_traffic_v16",
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
-           "cls_port_classes"]
+           "cls_port_classes", "cls_reach_hops"]
 
 
 class ClsRule(C.Structure):
@@ -113,6 +113,15 @@ class ReachPortsOut(C.Structure):
     _fields_ = [("ranges", C.c_void_p), ("cap", C.c_uint64), ("n_ranges", C.c_void_p), ("runs_out", C.c_void_p),
                 ("allow_ports_out", C.c_void_p), ("hist_out", C.c_void_p), ("n_classes", C.c_void_p)]
 
+
+class ReachHopsOut(C.Structure):
+    """cls_reach_hops_out: the outputs of cls_reach_hops, each optional."""
+    _fields_ = [("hops_out", C.c_void_p), ("reach_out", C.c_void_p), ("exposed_out", C.c_void_p),
+                ("level_out", C.c_void_p), ("closure_out", C.c_void_p)]
+
+
+# cls_reach_hops: not reached within max_hops
+HOPS_NONE = 255
 
 # cls_port_range as a numpy structured dtype (16 bytes)
 PORT_RANGE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("port_lo", "<u2"), ("port_hi", "<u2"), ("action", "u1"),
@@ -252,6 +261,7 @@ def bind(path: str, strict: bool = True):
         "cls_reach_diff": (C.c_int, [vp, C.POINTER(ReachSpec), vp, C.POINTER(ReachDiffOut), u32, vp]),
         "cls_reach_ports": (C.c_int, [vp, C.POINTER(ReachSpec), C.POINTER(ReachPortsOut), u32, vp]),
         "cls_port_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
+        "cls_reach_hops": (C.c_int, [vp, C.POINTER(ReachSpec), vp, u32, C.POINTER(ReachHopsOut), u32, vp]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -250,6 +250,11 @@ struct cls_engine {
     // ports per pair of a host call, the u64 histogram (its tiles, records,
     // chunk counts and total use the matrix's and the diff's buffers)
     DevBuf r_runs, r_pallow, r_phist;
+    // cls_reach_hops (reach.cpp), under the same rule: the adjacency bitmap
+    // (N x W u64 words, cleared per call) and a host call's outputs -- hops
+    // bytes, u32 reach and exposed counts, the u64 level histogram, the
+    // closure bitmap (a host matrix's tiles use r_base)
+    DevBuf r_adj, r_hhops, r_hreach, r_hexposed, r_hlevel, r_hclosure;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

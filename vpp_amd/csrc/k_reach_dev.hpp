@@ -1,6 +1,7 @@
 // Device code shared by the reachability matrix's units (k_reach.hip,
-// k_reach_diff.hip): a tile's cell arithmetic (kernels.hpp ReachTile), the
-// wave sum and the launches' grid.
+// k_reach_diff.hip, k_reach_ports.hip, k_reach_hops.hip): a tile's cell
+// arithmetic (kernels.hpp ReachTile), the wave sum and OR, and the launches'
+// grid.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,17 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// OR over the wave's 64 lanes of a 64-bit word
+__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
+    uint32_t lo = uint32_t(v), hi = uint32_t(v >> 32);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo |= __shfl_xor(lo, o, 64);
+        hi |= __shfl_xor(hi, o, 64);
+    }
+    return (unsigned long long)hi << 32 | lo;
 }
 
 // memory-bound, grid-stride: at most 8 workgroups per CU

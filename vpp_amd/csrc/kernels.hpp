@@ -481,6 +481,28 @@ hipError_t launch_reach_ports_emit(const ReachPortsTile& t, const uint8_t* verdi
                                    const unsigned long long* chunk_base, uint4* ranges, unsigned long long cap,
                                    int n_cu, hipStream_t s);
 
+// ---- the hop closure (k_reach_hops.hip; contivcls.h cls_reach_hops) --------
+// fold: the tile's CLS_CONN_ALLOW cells off the diagonal as bits of the
+// adjacency bitmap adj[N][W], W = (N + 63) / 64 -- bit (d & 63) of word
+// s W + (d >> 6), whatever the cell's probe (the union over probes).  verdict:
+// the tile's n bytes (no alignment needed).  A wave takes 64 consecutive
+// cells, builds each touched word from a ballot and ORs it in once.
+hipError_t launch_reach_adj_fold(const ReachTile& t, const uint8_t* verdict, unsigned long long* adj, int n_cu,
+                                 hipStream_t s);
+// bfs: the level-synchronous breadth-first search from every source over adj,
+// at most max_hops (1 .. 254) levels.  A workgroup owns `rows` (4, 8 or 16)
+// consecutive source rows from level 1 to the end, their reached / frontier /
+// next bit rows in LDS, and writes their outputs, each of which may be null:
+// hops[s N + d] (every byte once: 0 on the diagonal, the level, or 255),
+// reach[s], closure[s W + w]; it adds to exposed[d] and levels[256], which
+// the caller cleared.  No workgroup waits for another.
+constexpr uint32_t kHopsBlock = 256;
+size_t reach_hops_lds(uint32_t n_ep, uint32_t rows);      // the launch's LDS bytes
+uint32_t reach_hops_rows(uint32_t n_ep, uint32_t want);   // want (0: 4, the measured best) cut to what fits LDS
+hipError_t launch_reach_hops_bfs(uint32_t n_ep, uint32_t max_hops, uint32_t rows, const unsigned long long* adj,
+                                 uint8_t* hops, uint32_t* reach, uint32_t* exposed, unsigned long long* levels,
+                                 unsigned long long* closure, hipStream_t s);
+
 struct TrafficDev {
     uint64_t seed;
     uint32_t pct_pod, pct_dst, pct_port, pct_icmp;

@@ -97,6 +97,14 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
         o.reach_tile = reset ? d.reach_tile : uint32_t((x + 1023) & ~1023ll);
         return true;
     }
+    if (k == "hops_rows") {
+        if (!reset && x != 0 && x != 4 && x != 8 && x != 16) {
+            why = "option hops_rows: 0 (the default), 4, 8 or 16 source rows per workgroup";
+            return false;
+        }
+        o.hops_rows = reset ? d.hops_rows : uint32_t(x);
+        return true;
+    }
     if (k == "orient") {
         const std::string v = reset ? "" : value;
         if (!reset && v != "src" && v != "dst") {

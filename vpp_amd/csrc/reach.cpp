@@ -8,7 +8,8 @@
 // reduce launch and a host call's copy back; at the end the accumulators'
 // copy to the outputs.  cls_reach_diff is the same call with a baseline: per
 // tile it adds the diff launches (k_reach_diff.hip) behind the reduce launch,
-// and its own outputs at the end.
+// and its own outputs at the end.  cls_reach_ports and cls_reach_hops, on the
+// same tile pipeline and scratch, have their sections below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +47,8 @@ struct ReachCall {
     uint64_t* n_changes = nullptr;
     uint64_t* trans_out = nullptr;
     uint32_t* changed_out = nullptr;
+    // cls_reach_hops: the adjacency bitmap every tile's ALLOW cells are folded into
+    unsigned long long* adj = nullptr;
     // the chunk counts and their scan: for the records, the total, and a
     // device call's in-place stores (made by the emit launch)
     bool scan() const { return changes || n_changes || (dev && inplace); }
@@ -76,6 +79,28 @@ static int reach_spec_ifs(cls_engine* e, const cls_reach_spec* sp) {
     return CLS_OK;
 }
 
+// N, P and the cell bound.
+static int reach_cells(cls_engine* e, const cls_reach_spec* sp, ReachCall& R) {
+    R.N = sp->n_endpoints;
+    R.P = sp->n_probes;
+    // (N^2 first: P x N^2 <= 2^36 with P >= 1 needs N <= 2^18)
+    if (R.N > (1u << 18) || uint64_t(R.N) * R.N > kReachMaxCells / R.P)
+        return fail(e, CLS_E_INVAL, "reach matrix above 2^36 cells");
+    R.cells = uint64_t(R.N) * R.N * R.P;
+    return CLS_OK;
+}
+// The evaluator's flags, the tile, the stream and the tables' layout of a
+// call whose arguments passed.
+static void reach_resolve(cls_engine* e, uint32_t flags, void* stream, ReachCall& R) {
+    R.mode = flags & (CLS_F_COUNT | CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR);
+    R.tile = e->opts.reach_tile;
+    R.s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    R.off_addr = (size_t(R.N) * 4 + 15) & ~size_t(15);
+    R.off_probe = R.off_addr + size_t(R.N) * (R.k16 ? 16 : 4);
+    R.off_probe = (R.off_probe + 15) & ~size_t(15);
+    R.tab_bytes = R.off_probe + size_t(R.P) * sizeof(uint2);
+}
+
 // Checks everything a refusal can depend on: no device work is queued before
 // this returns CLS_OK.
 static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdict_out, uint64_t* hist_out,
@@ -88,27 +113,17 @@ static int reach_inputs(cls_engine* e, const cls_reach_spec* sp, uint8_t* verdic
         return fail(e, CLS_E_INVAL, "reach matrix without an output");
     if (!R.base && !verdict_out && !(flags & CLS_F_NO_VERDICT))
         return fail(e, CLS_E_INVAL, "verdict_out is NULL without CLS_F_NO_VERDICT");
-    R.N = sp->n_endpoints;
-    R.P = sp->n_probes;
-    // (N^2 first: P x N^2 <= 2^36 with P >= 1 needs N <= 2^18)
-    if (R.N > (1u << 18) || uint64_t(R.N) * R.N > kReachMaxCells / R.P)
-        return fail(e, CLS_E_INVAL, "reach matrix above 2^36 cells");
-    R.cells = uint64_t(R.N) * R.N * R.P;
+    rc = reach_cells(e, sp, R);
+    if (rc != CLS_OK) return rc;
     R.dev = flags & CLS_F_DEVICE;
     if (R.dev && (!aligned(verdict_out, 16) || !aligned(hist_out, 8) || !aligned(allow_out, 4)))
         return fail(e, CLS_E_INVAL, "device outputs: verdict_out 16-byte, hist_out 8-byte, allow_out 4-byte aligned");
     rc = reach_spec_ifs(e, sp);
     if (rc != CLS_OK) return rc;
-    R.mode = flags & (CLS_F_COUNT | CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR);
-    R.tile = e->opts.reach_tile;
-    R.s = stream ? static_cast<hipStream_t>(stream) : e->stream;
     R.verdict_out = verdict_out;
     R.hist_out = hist_out;
     R.allow_out = allow_out;
-    R.off_addr = (size_t(R.N) * 4 + 15) & ~size_t(15);
-    R.off_probe = R.off_addr + size_t(R.N) * (R.k16 ? 16 : 4);
-    R.off_probe = (R.off_probe + 15) & ~size_t(15);
-    R.tab_bytes = R.off_probe + size_t(R.P) * sizeof(uint2);
+    reach_resolve(e, flags, stream, R);
     return CLS_OK;
 }
 
@@ -136,17 +151,24 @@ static int reach_diff_inputs(cls_engine* e, const cls_reach_diff_out* o, ReachCa
     return CLS_OK;
 }
 
-// The call's tables (one blob), uploaded once per call from the engine's copy
-// (the caller's arrays are not read after this); nothing is copied when the
-// last call's blob is the same.  Orders the call behind the last
-// stream-ordered batch of another stream, which may still use the scratch.
-static int reach_upload_tab(cls_engine* e, const ReachCall& R, std::vector<uint8_t>& tab) {
+// Orders the call behind the last stream-ordered batch of another stream,
+// which may still use the scratch.
+static int reach_follow(cls_engine* e, const ReachCall& R) {
     HIPC(e, hipSetDevice(e->device));
     if (e->conn_last && e->conn_last != R.s) {
         if (!e->conn_sync_ev) HIPC(e, hipEventCreateWithFlags(&e->conn_sync_ev, hipEventDisableTiming));
         HIPC(e, hipEventRecord(e->conn_sync_ev, e->conn_last));
         HIPC(e, hipStreamWaitEvent(R.s, e->conn_sync_ev, 0));
     }
+    return CLS_OK;
+}
+
+// The call's tables (one blob), uploaded once per call from the engine's copy
+// (the caller's arrays are not read after this); nothing is copied when the
+// last call's blob is the same.  The call's first device work (reach_follow).
+static int reach_upload_tab(cls_engine* e, const ReachCall& R, std::vector<uint8_t>& tab) {
+    const int frc = reach_follow(e, R);
+    if (frc != CLS_OK) return frc;
     const void* was = e->r_tab.p;
     HIPC(e, reach_grow(e, e->r_tab, tab.size()));
     if (e->r_tab.p == was && e->reach_up == tab) return CLS_OK;
@@ -272,6 +294,7 @@ static int reach_tile(cls_engine* e, const ReachCall& R, uint64_t first, uint32_
     if (R.reduce())
         HIPC(e, launch_reach_reduce(T, v, R.hist_out ? e->r_hist.as<unsigned long long>() + 4 * uint64_t(T.p0) : nullptr,
                                     R.allow_out ? e->r_allow.as<uint32_t>() + row : nullptr, e->n_cu, R.s));
+    if (R.adj) HIPC(e, launch_reach_adj_fold(T, v, R.adj, e->n_cu, R.s));
     if (R.base) {
         const int drc = reach_diff_tile(e, R, T, first, row, v);
         if (drc != CLS_OK) return drc;
@@ -610,5 +633,159 @@ extern "C" int cls_reach_ports(cls_engine* e, const cls_reach_spec* spec, const 
     for (uint64_t pair = 0; rc == CLS_OK && pair < C.pairs; pair += C.per_tile)
         rc = ports_tile(e, C, pair, uint32_t(std::min(C.per_tile, C.pairs - pair)));
     if (rc == CLS_OK) rc = ports_outputs(e, C);
+    return rc;
+}
+
+// ---- cls_reach_hops: multi-hop closure and blast radius of the matrix -----
+// The graph: an edge s -> d (s != d) where some probe's cell is
+// CLS_CONN_ALLOW.  Per tile the fold launch (k_reach_hops.hip) ORs the tile's
+// ALLOW cells into the adjacency bitmap r_adj -- behind the evaluator in
+// reach_tile, or alone over a caller's matrix -- and one launch at the end runs
+// the breadth-first search from every source and writes every output.
+
+struct HopsCall {
+    ReachCall R;
+    const uint8_t* matrix = nullptr;       // null: the matrix of the spec is evaluated
+    uint32_t H = 0, W = 0, rows = 0;       // levels (1 .. 254); words per bit row; source rows per workgroup
+    cls_reach_hops_out o{};
+};
+
+// Checks everything a refusal can depend on: no device work is queued before
+// this returns CLS_OK.
+static int hops_inputs(cls_engine* e, const cls_reach_spec* sp, const uint8_t* matrix, uint32_t max_hops,
+                       const cls_reach_hops_out* o, uint32_t flags, void* stream, HopsCall& C) {
+    ReachCall& R = C.R;
+    if (matrix) {
+        if (!sp->n_endpoints || !sp->n_probes) return fail(e, CLS_E_INVAL, "reach hops without endpoints or probes");
+        if (flags & (CLS_F_COUNT | CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR))
+            return fail(e, CLS_E_INVAL, "reach hops over a matrix evaluates nothing: no CLS_F_COUNT, CLS_F_CONN_CLS "
+                                        "or CLS_F_FORCE_LINEAR");
+    } else {
+        const int rc = reach_spec(e, sp, R);
+        if (rc != CLS_OK) return rc;
+        if (!sp->dport) return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
+    }
+    if (flags & CLS_F_NO_VERDICT) return fail(e, CLS_E_INVAL, "reach hops: no CLS_F_NO_VERDICT");
+    if (!o->hops_out && !o->reach_out && !o->exposed_out && !o->level_out && !o->closure_out)
+        return fail(e, CLS_E_INVAL, "reach hops without hops_out, reach_out, exposed_out, level_out or closure_out");
+    if (max_hops > 254) return fail(e, CLS_E_INVAL, "reach hops: max_hops %u above 254", max_hops);
+    int rc = reach_cells(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    if (R.N > 32768) return fail(e, CLS_E_INVAL, "reach hops above 32768 endpoints (N %u)", R.N);
+    R.dev = flags & CLS_F_DEVICE;
+    if (R.dev && (!aligned(matrix, 16) || !aligned(o->hops_out, 16) || !aligned(o->level_out, 8) ||
+                  !aligned(o->closure_out, 8) || !aligned(o->reach_out, 4) || !aligned(o->exposed_out, 4)))
+        return fail(e, CLS_E_INVAL, "device reach hops: matrix, hops_out 16-byte, level_out, closure_out 8-byte, "
+                                    "reach_out, exposed_out 4-byte aligned");
+    if (!matrix) {
+        rc = reach_spec_ifs(e, sp);
+        if (rc != CLS_OK) return rc;
+    }
+    reach_resolve(e, flags, stream, R);
+    C.matrix = matrix;
+    C.H = max_hops ? max_hops : 254;
+    C.W = (R.N + 63) / 64;
+    C.rows = reach_hops_rows(R.N, e->opts.hops_rows);
+    C.o = *o;
+    return CLS_OK;
+}
+
+// Where the launch writes: the caller's device memory, or the engine's for a
+// host call.
+static uint8_t* hops_hops(cls_engine* e, const HopsCall& C) {
+    return !C.o.hops_out ? nullptr : C.R.dev ? C.o.hops_out : e->r_hhops.as<uint8_t>();
+}
+static uint32_t* hops_reach(cls_engine* e, const HopsCall& C) {
+    return !C.o.reach_out ? nullptr : C.R.dev ? C.o.reach_out : e->r_hreach.as<uint32_t>();
+}
+static uint32_t* hops_exposed(cls_engine* e, const HopsCall& C) {
+    return !C.o.exposed_out ? nullptr : C.R.dev ? C.o.exposed_out : e->r_hexposed.as<uint32_t>();
+}
+static unsigned long long* hops_levels(cls_engine* e, const HopsCall& C) {
+    return !C.o.level_out ? nullptr
+           : C.R.dev      ? reinterpret_cast<unsigned long long*>(C.o.level_out)
+                          : e->r_hlevel.as<unsigned long long>();
+}
+static unsigned long long* hops_closure(cls_engine* e, const HopsCall& C) {
+    return !C.o.closure_out ? nullptr
+           : C.R.dev        ? reinterpret_cast<unsigned long long*>(C.o.closure_out)
+                            : e->r_hclosure.as<unsigned long long>();
+}
+
+// The bitmap (cleared), a host matrix's tile, a host call's outputs; the
+// accumulators cleared.  The evaluating form's tile arrays: reach_scratch.
+static int hops_scratch(cls_engine* e, const HopsCall& C) {
+    const ReachCall& R = C.R;
+    const size_t bits = size_t(R.N) * C.W * 8;
+    HIPC(e, reach_grow(e, e->r_adj, bits));
+    HIPC(e, hipMemsetAsync(e->r_adj.p, 0, bits, R.s));
+    if (C.matrix && !R.dev) HIPC(e, reach_grow(e, e->r_base, size_t(std::min(R.tile, R.cells))));
+    if (!R.dev) {
+        if (C.o.hops_out) HIPC(e, reach_grow(e, e->r_hhops, size_t(R.N) * R.N));
+        if (C.o.reach_out) HIPC(e, reach_grow(e, e->r_hreach, size_t(R.N) * 4));
+        if (C.o.exposed_out) HIPC(e, reach_grow(e, e->r_hexposed, size_t(R.N) * 4));
+        if (C.o.level_out) HIPC(e, reach_grow(e, e->r_hlevel, 256 * 8));
+        if (C.o.closure_out) HIPC(e, reach_grow(e, e->r_hclosure, bits));
+    }
+    if (uint32_t* p = hops_exposed(e, C)) HIPC(e, hipMemsetAsync(p, 0, size_t(R.N) * 4, R.s));
+    if (unsigned long long* p = hops_levels(e, C)) HIPC(e, hipMemsetAsync(p, 0, 256 * 8, R.s));
+    return CLS_OK;
+}
+
+// One tile of a caller's matrix: cells [first, first + n), a host matrix's
+// through the scratch.
+static int hops_fold_tile(cls_engine* e, const HopsCall& C, uint64_t first, uint32_t n) {
+    const ReachCall& R = C.R;
+    const uint64_t row = first / R.N;
+    const ReachTile T{R.N, uint32_t(row / R.N), uint32_t(row % R.N), uint32_t(first % R.N), n};
+    const uint8_t* v = C.matrix + first;
+    if (!R.dev) {
+        HIPC(e, hipMemcpyAsync(e->r_base.p, v, n, hipMemcpyHostToDevice, R.s));
+        v = e->r_base.as<uint8_t>();
+    }
+    HIPC(e, launch_reach_adj_fold(T, v, R.adj, e->n_cu, R.s));
+    return CLS_OK;
+}
+
+// The search, and a host call's results through the engine's buffers; a
+// device call is stream-ordered (conn_last).
+static int hops_outputs(cls_engine* e, const HopsCall& C) {
+    const ReachCall& R = C.R;
+    HIPC(e, launch_reach_hops_bfs(R.N, C.H, C.rows, R.adj, hops_hops(e, C), hops_reach(e, C), hops_exposed(e, C),
+                                  hops_levels(e, C), hops_closure(e, C), R.s));
+    if (R.dev) {
+        e->conn_last = R.s;
+        return CLS_OK;
+    }
+    const hipMemcpyKind kind = hipMemcpyDeviceToHost;
+    if (C.o.hops_out) HIPC(e, hipMemcpyAsync(C.o.hops_out, e->r_hhops.p, size_t(R.N) * R.N, kind, R.s));
+    if (C.o.reach_out) HIPC(e, hipMemcpyAsync(C.o.reach_out, e->r_hreach.p, size_t(R.N) * 4, kind, R.s));
+    if (C.o.exposed_out) HIPC(e, hipMemcpyAsync(C.o.exposed_out, e->r_hexposed.p, size_t(R.N) * 4, kind, R.s));
+    if (C.o.level_out) HIPC(e, hipMemcpyAsync(C.o.level_out, e->r_hlevel.p, 256 * 8, kind, R.s));
+    if (C.o.closure_out) HIPC(e, hipMemcpyAsync(C.o.closure_out, e->r_hclosure.p, size_t(R.N) * C.W * 8, kind, R.s));
+    HIPC(e, hipStreamSynchronize(R.s));
+    e->conn_last = nullptr;
+    return CLS_OK;
+}
+
+extern "C" int cls_reach_hops(cls_engine* e, const cls_reach_spec* spec, const uint8_t* matrix, uint32_t max_hops,
+                              const cls_reach_hops_out* out, uint32_t flags, void* stream) {
+    if (!e || !spec) return CLS_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    if (!out) return fail(e, CLS_E_INVAL, "reach hops without outputs");
+    HopsCall C;
+    ReachCall& R = C.R;
+    int rc = hops_inputs(e, spec, matrix, max_hops, out, flags, stream, C);
+    if (rc != CLS_OK) return rc;
+    rc = matrix ? reach_follow(e, R) : reach_upload(e, spec, R);
+    if (rc == CLS_OK && !matrix) rc = reach_scratch(e, R);
+    if (rc == CLS_OK) rc = hops_scratch(e, C);
+    R.adj = e->r_adj.as<unsigned long long>();
+    for (uint64_t first = 0; rc == CLS_OK && first < R.cells; first += R.tile) {
+        const uint32_t n = uint32_t(std::min(R.tile, R.cells - first));
+        rc = matrix ? hops_fold_tile(e, C, first, n) : reach_tile(e, R, first, n);
+    }
+    if (rc == CLS_OK) rc = hops_outputs(e, C);
     return rc;
 }

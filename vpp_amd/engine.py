@@ -36,6 +36,8 @@ TCP, UDP, ICMP = 0, 1, 2
 ReachDiff = collections.namedtuple("ReachDiff", "verdicts changes n_changes trans changed hist allow")
 # Engine.reach_ports's result
 ReachPorts = collections.namedtuple("ReachPorts", "ranges n_ranges runs allow_ports hist n_classes")
+# Engine.reach_hops's result; what was not asked for is None
+ReachHops = collections.namedtuple("ReachHops", "hops reach exposed levels closure")
 
 
 def _is_torch(x) -> bool:
@@ -768,6 +770,87 @@ class Engine:
         self._check(fn(self.h, C.byref(spec), C.byref(o), flags | _abi.F_DEVICE, s))
         return ReachPorts(*res, int(k[0]))
 
+    def reach_hops(self, if_ids, addrs, protos, sports, dports, max_hops: int = 0, matrix=None, mode: str = "auto",
+                   count: bool = False, hops: bool = True, reach: bool = True, exposed: bool = True,
+                   levels: bool = True, closure: bool = False, out=None, stream=None):
+        """The multi-hop closure of the reachability matrix (cls_reach_hops):
+        endpoint s has an edge to d != s when some probe's cell (p, s, d) is
+        CONN_ALLOW.  Returns ReachHops(hops [N, N] u8: the length of a
+        shortest path s -> d if at most ``max_hops`` (0: 254), else 255, and 0
+        on the diagonal; reach [N] u32: the destinations a source reaches;
+        exposed [N] u32: the sources that reach a destination; levels [256]
+        u64: pairs per hops value; closure [N, (N + 63) // 64] u64: bit d of
+        row s set when s reaches d or s == d); what is not wanted is None.
+        ``matrix`` None: the matrix of reach_matrix's arguments is evaluated on
+        the device (mode and count as there) and never stored.  ``matrix`` a
+        [P, N, N] uint8 array of an earlier call: it is folded instead, nothing
+        is evaluated, and if_ids, addrs and the probe arrays may be None.  out
+        None: numpy results (the call returns with them), for a numpy matrix
+        or none.  out a sequence (hops, reach, exposed, levels, closure) of
+        contiguous torch GPU tensors -- u8, 4-, 4-, 8-, 8-byte elements; None
+        for a wanted one allocates it -- selects the device form, which a
+        torch GPU matrix requires: the call only enqueues on ``stream``
+        (default: the engine's) and returns the tensors."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        if count:
+            flags |= _abi.F_COUNT
+        if matrix is None:
+            ids = np.ascontiguousarray(if_ids, np.uint32)
+            a = np.asarray(addrs)
+            v16 = a.ndim == 2
+            a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+            pr, sp = np.ascontiguousarray(protos, np.uint8), np.ascontiguousarray(sports, np.uint16)
+            dp = np.ascontiguousarray(dports, np.uint16)
+            n, p = len(ids), len(pr)
+            if len(a) != n or len(sp) != p or len(dp) != p:
+                raise ClsError("reach hops: N interface ids and addresses, P protocols and ports")
+            spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                                  _ptr(a) if v16 else None, p, _ptr(pr), _ptr(sp), _ptr(dp))
+        else:
+            if _is_torch(matrix):
+                import torch
+                if out is None:
+                    raise ClsError("reach hops: a GPU matrix needs the device form (out)")
+                ok = matrix.is_cuda and matrix.is_contiguous() and matrix.dtype == torch.uint8
+            else:
+                if out is not None:
+                    raise ClsError("reach hops: the device form takes a GPU matrix")
+                matrix = np.asarray(matrix)
+                ok = matrix.dtype == np.uint8 and matrix.flags.c_contiguous
+            if not ok or matrix.ndim != 3 or matrix.shape[1] != matrix.shape[2]:
+                raise ClsError("reach hops: matrix must be a contiguous uint8 array of shape (P, N, N)")
+            p, n = int(matrix.shape[0]), int(matrix.shape[1])
+            spec = _abi.ReachSpec(_abi.AF_V4, n, None, None, None, p, None, None, None)
+        w = (n + 63) // 64
+        want = (hops, reach, exposed, levels, closure)
+        shapes = ((n, n), (n,), (n,), (256,), (n, w))
+        if out is None:
+            res = [np.zeros(sh, dt) if wt else None
+                   for wt, sh, dt in zip(want, shapes, (np.uint8, np.uint32, np.uint32, np.uint64, np.uint64))]
+            s = None
+        else:
+            import torch
+            flags |= _abi.F_DEVICE
+            res = list(out)
+            if len(res) != 5:
+                raise ClsError("reach hops: out is (hops, reach, exposed, levels, closure)")
+            kinds = ((torch.uint8, 1), (torch.int32, 4), (torch.int32, 4), (torch.int64, 8), (torch.int64, 8))
+            for k, (wt, sh, (dt, sz)) in enumerate(zip(want, shapes, kinds)):
+                if not wt:
+                    res[k] = None
+                elif res[k] is None:
+                    res[k] = torch.empty(sh, dtype=dt, device="cuda")
+                elif not (_is_torch(res[k]) and res[k].is_cuda and res[k].is_contiguous() and
+                          res[k].element_size() == sz and tuple(res[k].shape) == sh):
+                    raise ClsError("reach hops: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                                   "elements" % (k, sh, sz))
+            s = None
+            if stream is not None:
+                s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.ReachHopsOut(*[_ptr(x) for x in res])
+        self._check(_abi.lib().cls_reach_hops(self.h, C.byref(spec), _ptr(matrix), int(max_hops), C.byref(o), flags, s))
+        return ReachHops(*res)
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -1151,6 +1234,29 @@ class ACLEngine:
                                            hist=False, allow=False)
         at = np.array([e[0] for e in eps])
         out[:, at[:, None], at[None, :]] = v
+        return out
+
+    def connection_hops(self, pods, probes, max_hops: int = 0) -> np.ndarray:
+        """Lateral movement: a [len(pods), len(pods)] uint8 array whose cell
+        (s, d) is the least number of connections, each CONN_ALLOW under some
+        probe of ``probes`` ((proto, sport, dport) triples), that lead from
+        pods[s] to pods[d] through other pods of ``pods`` -- 0 for s == d, 255
+        when there is no such path of at most ``max_hops`` (0: 254)
+        connections.  One engine call (Engine.reach_hops) over the pods'
+        endpoints; the matrix is never brought to the host.  A pod the
+        reference fails before testConnection (connection_matrix) has no
+        edges: its row and column are 255 but for the diagonal."""
+        n = len(pods)
+        out = np.full((n, n), _abi.HOPS_NONE, np.uint8)
+        out[np.arange(n), np.arange(n)] = 0
+        eps = self._matrix_endpoints(pods)
+        if not eps or not probes:
+            return out
+        pr = np.array(probes, np.int64).reshape(-1, 3)
+        r = self.engine.reach_hops([e[1] for e in eps], self._matrix_addrs(eps), pr[:, 0], pr[:, 1], pr[:, 2],
+                                   max_hops=max_hops, reach=False, exposed=False, levels=False)
+        at = np.array([e[0] for e in eps])
+        out[at[:, None], at[None, :]] = r.hops
         return out
 
     def connection_ports(self, pods, protocol, src_port):
