@@ -703,7 +703,9 @@ int cls_batch_counters(cls_batch* b, uint64_t* out, uint32_t n_out);
 /* testConnection over a CLS_BATCH_CONN batch (as cls_connect_batch with
  * device memory; ConnectionAction into CLS_BF_VERDICT), every device its
  * shard; CLS_F_COUNT counts into each device's copy of the tables'
- * connection counters (cls_conn_counters sums them).  Returns when done. */
+ * connection counters (cls_conn_counters sums them).  Returns once the work
+ * is enqueued on every device's engine stream: cls_batch_wait,
+ * cls_batch_download and cls_conn_counters order behind it. */
 int cls_batch_connect(cls_engine* e, cls_batch* b, uint32_t flags);
 /* Wait for every device's work on the batch. */
 int cls_batch_wait(cls_batch* b);

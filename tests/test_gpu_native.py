@@ -13,9 +13,11 @@ multi-device engines and the in-library RCCL counter all-reduce
   eight peer engines, no communicator, host-summed counters): tables compiled
   once and replicated to every shard's engine, verdicts and counters equal to
   one device's and to the oracle's, on a ragged batch.
-- Uploads (pinned mirror, staged from pageable memory in several 32 MiB
-  chunks) and downloads round-trip; connection batches sharded over eight
+- Uploads (pinned mirror, staged from pageable memory, one 32 MiB chunk a
+  shard) and downloads round-trip; connection batches sharded over four
   shards equal the oracle's testConnection, and their counters the oracle's.
+- The 16-byte layout, windows, shard edges and several staging chunks:
+  tests/test_gpu_batches.py.
 """
 import json
 import os
@@ -122,7 +124,9 @@ def test_eight_shards_replicate_tables_and_merge_counters():
 
 def test_mirror_and_staged_upload_round_trip():
     acl, spec, _ = workload.config(2)
-    n = (9 << 20) + 3                      # 36 MiB of addresses: two staging chunks
+    # 36 MiB of addresses over two shards: 18 MiB each, one staging chunk a
+    # shard (several chunks: test_gpu_batches.py test_three_staging_chunks)
+    n = (9 << 20) + 3
     tr = oracle.gen_traffic_v4(spec, 11, n)
     ov, oc = _oracle(acl, tr)
     eng = Engine(devices=[0, 0])

@@ -696,7 +696,9 @@ int cls_classify_batch(cls_engine* e, uint32_t table_id, cls_batch* b, uint64_t*
         }
         if (s.rec_red[k]) HIPC(e, hipStreamWaitEvent(d->stream, s.reduced[k], 0));
         const cls_pkt_soa p = shard_soa(b, s);
-        const int rc = classify_locked(d, table_id, &p, s.n, fld<uint8_t>(s, CLS_BF_VERDICT),
+        // CLS_F_NO_VERDICT: counters only, the batch's verdict field stays as it is
+        uint8_t* vo = (flags & CLS_F_NO_VERDICT) ? nullptr : fld<uint8_t>(s, CLS_BF_VERDICT);
+        const int rc = classify_locked(d, table_id, &p, s.n, vo,
                                        s.ctr[k].as<uint64_t>(), pass | CLS_F_DEVICE, d->stream);
         if (rc != CLS_OK) return relay(e, d, rc);
         // the all-reduce's dependency (an event record costs the stream a
