@@ -185,6 +185,11 @@ int cls_engine_devices(const cls_engine* e, uint32_t* n_devices);
  * stream floors, raw device pointers of that device); configuration calls on
  * it are refused (configure through `e`). */
 int cls_device_engine(cls_engine* e, uint32_t index, cls_engine** dev);
+/* The message of the engine's last failing call.  The pointer is the engine's
+ * own string: it is valid only until the next failing call on that engine
+ * from any thread, which rewrites and may reallocate it.  A caller that
+ * shares the engine with other threads goes by the return code and reads the
+ * text only where it knows no other call can fail meanwhile. */
 const char* cls_last_error(const cls_engine* e);
 int cls_abi_version(void);
 /* Diagnostics, tests and measurements: one tuning switch of the engine (and
@@ -192,8 +197,9 @@ int cls_abi_version(void);
  * The switches force compiler choices (list_mode, list_mode_max, trie, wide,
  * orient=src|dst, lds_budget, src_search, phash_dense, v16_src_search,
  * v16_src_trie) for later cls_table_put / cls_acl_put compiles, and launch
- * plans (other_cap, wg_per_cu, conn_bitmap, conn_pair, conn_pair16, conn_pre_rules,
- * conn_pre_narrow, pair_qcap, pair_lq, pair_other_global, conn_no_lds,
+ * plans (other_cap, wg_per_cu, fold_split, conn_bitmap, conn_pair, conn_pair16, conn_pre_rules,
+ * conn_pre_narrow, conn_wg_per_cu, conn_wg768, pair_qcap, pair_lq, pair_other_global,
+ * pair_other_late, pair_o4, pair_map_lds, pair_class, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
  * up to a multiple of 1024 --, hops_rows, debug_modes, debug_conn, debug_floor) for
@@ -263,15 +269,20 @@ int cls_classify_rules(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pkts
                        uint32_t flags, void* stream);
 
 /* Milliseconds of the last classify kernel (CLS_F_TIMING), measured with HIP
- * events on the launch stream.  Blocks until that kernel has finished. */
+ * events on the launch stream.  Blocks until that kernel has finished.
+ * Serialised with the other calls like them: among concurrent timed calls it
+ * reports one whole call's pair, the last one enqueued. */
 int cls_last_kernel_ms(cls_engine* e, float* ms);
 /* Every classify kernel timed (CLS_F_TIMING) since the last reset: up to `cap`
  * durations in launch order; *count = number recorded.  Recording enqueues
- * only events (no host synchronisation); reading blocks on the last one. */
+ * only events (no host synchronisation); reading blocks until every one has
+ * finished (timed calls on several streams finish in any order). */
 int cls_kernel_times(cls_engine* e, float* ms, uint32_t cap, uint32_t* count);
 /* The same kernels' start times, milliseconds after the first one's: the
  * differences are the launch-to-launch period of a stream of timed calls
- * (each kernel stamps its own start, so no event marker sits between them). */
+ * (each kernel stamps its own start, so no event marker sits between them).
+ * Kernels timed on different streams start in any order: launch order, in
+ * which both calls list them, is start order on one stream only. */
 int cls_kernel_starts(cls_engine* e, float* ms, uint32_t cap, uint32_t* count);
 int cls_kernel_times_reset(cls_engine* e);
 

@@ -26,12 +26,13 @@ int orc_classify_fast(const orc_ctable*, int, const void*, const void*, const ui
                       uint8_t*, uint64_t*, int);
 }
 
-static int compile(int (*fn)(const cls_rule*, uint32_t, void*, uint64_t, uint64_t*), const std::vector<cls_rule>& r) {
+static int compile(int (*fn)(const cls_rule*, uint32_t, void*, uint64_t, uint64_t*, const char*),
+                   const std::vector<cls_rule>& r) {
     uint64_t need = 0;
-    int rc = fn(r.data(), uint32_t(r.size()), nullptr, 0, &need);
+    int rc = fn(r.data(), uint32_t(r.size()), nullptr, 0, &need, nullptr);
     if (rc != CLS_OK) return rc;
     std::vector<uint8_t> blob(need);
-    rc = fn(r.data(), uint32_t(r.size()), blob.data(), need, &need);
+    rc = fn(r.data(), uint32_t(r.size()), blob.data(), need, &need, nullptr);
     return rc;
 }
 

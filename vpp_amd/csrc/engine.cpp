@@ -1037,7 +1037,12 @@ int cls_stream_floor_shapes(cls_engine* e, const cls_pkt_soa* pk, uint64_t n, ui
 
 int cls_last_kernel_ms(cls_engine* e, float* ms) {
     if (!e || !ms) return CLS_E_INVAL;
+    // the pair of the last timed call, read under the mutex: a concurrent timed
+    // call hands out and records a new pair inside its own locked section
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
     if (!e->timed) return fail(e, CLS_E_INVAL, "no timed classify recorded");
+    HIPC(e, hipSetDevice(e->device));
     HIPC(e, hipEventSynchronize(e->ev1));
     HIPC(e, hipEventElapsedTime(ms, e->ev0, e->ev1));
     return CLS_OK;
@@ -1048,7 +1053,8 @@ int cls_kernel_times(cls_engine* e, float* ms, uint32_t cap, uint32_t* count) {
     std::lock_guard<std::mutex> g(e->mu);
     *count = uint32_t(e->ev_used);
     if (e->ev_used == 0) return CLS_OK;
-    HIPC(e, hipEventSynchronize(e->ev_pool[e->ev_used - 1].second));
+    // every pair's end: timed calls on several streams finish in any order
+    for (size_t i = 0; i < e->ev_used; ++i) HIPC(e, hipEventSynchronize(e->ev_pool[i].second));
     for (size_t i = 0; i < e->ev_used && i < cap && ms; ++i)
         HIPC(e, hipEventElapsedTime(&ms[i], e->ev_pool[i].first, e->ev_pool[i].second));
     return CLS_OK;
@@ -1059,7 +1065,8 @@ int cls_kernel_starts(cls_engine* e, float* ms, uint32_t cap, uint32_t* count) {
     std::lock_guard<std::mutex> g(e->mu);
     *count = uint32_t(e->ev_used);
     if (e->ev_used == 0) return CLS_OK;
-    HIPC(e, hipEventSynchronize(e->ev_pool[e->ev_used - 1].second));
+    // every pair's end: timed calls on several streams finish in any order
+    for (size_t i = 0; i < e->ev_used; ++i) HIPC(e, hipEventSynchronize(e->ev_pool[i].second));
     for (size_t i = 0; i < e->ev_used && i < cap && ms; ++i)
         HIPC(e, hipEventElapsedTime(&ms[i], e->ev_pool[0].first, e->ev_pool[i].first));
     return CLS_OK;
@@ -1068,7 +1075,7 @@ int cls_kernel_starts(cls_engine* e, float* ms, uint32_t cap, uint32_t* count) {
 int cls_kernel_times_reset(cls_engine* e) {
     if (!e) return CLS_E_INVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->ev_used) HIPC(e, hipEventSynchronize(e->ev_pool[e->ev_used - 1].second));
+    for (size_t i = 0; i < e->ev_used; ++i) HIPC(e, hipEventSynchronize(e->ev_pool[i].second));
     e->ev_used = 0;
     return CLS_OK;
 }
