@@ -1108,6 +1108,131 @@ func (en *Engine) ReachHops(pods []podmodel.ID, probes []Probe, maxHops int) (*H
 	return out, nil
 }
 
+// ClassNone is Quot[p][c][c] of a class with one member (CLS_CLASS_NONE).
+const ClassNone = 255
+
+// Classes is the result of ReachClasses over N pods and P probes: the
+// connectivity map.  Class[i] is the class of pods[i], or -1 for a pod that
+// ConnectionPodToPod fails before testConnection (it is in no class); pods of
+// one class cannot be told apart by the probes: exchanging two of them leaves
+// the matrix of ReachMatrix unchanged.  Classes are numbered by their first
+// pod: Rep[c] is its index in pods, Size[c] the members.  Self[p*C+c] is the
+// ConnectionAction of a member of c to itself, Quot[(p*C+a)*C+b] the one from
+// any member of a to any member of b, and for a == b between two members of a
+// (ClassNone when a has one member).
+type Classes struct {
+	N, P, C int
+	Class   []int32
+	Rep     []uint32
+	Size    []uint32
+	Self    []uint8
+	Quot    []uint8
+	Rounds  int
+}
+
+// ReachClasses summarises the matrix of ReachMatrix's arguments in one engine
+// call (cls_reach_classes): the matrix is evaluated on the device and only the
+// classes and the P x C x C quotient come back.  The call is made with room
+// for 64 classes and once more with room for all when there are more.
+func (en *Engine) ReachClasses(pods []podmodel.ID, probes []Probe) (*Classes, error) {
+	en.Lock()
+	defer en.Unlock()
+	N, P := len(pods), len(probes)
+	out := &Classes{N: N, P: P, Class: make([]int32, N)}
+	for i := range out.Class {
+		out.Class[i] = -1
+	}
+	var strs cstrs
+	defer strs.free()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil {
+			continue
+		}
+		ifName, ok := en.podIf(pod, cfg)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	if n == 0 || P == 0 {
+		return out, nil
+	}
+	proto, sport, dport := make([]uint8, P), make([]uint16, P), make([]uint16, P)
+	for p, q := range probes {
+		proto[p], sport[p], dport[p] = uint8(q.Protocol), q.SrcPort, q.DstPort
+	}
+	a4, a16 := make([]uint32, 1), make([]byte, 16)
+	if v4 {
+		a4 = make([]uint32, n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To4()
+			a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+		}
+	} else {
+		a16 = make([]byte, 16*n)
+		for k := 0; k < n; k++ {
+			a := ips[k].To16()
+			if a == nil {
+				return nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+			}
+			copy(a16[16*k:], a)
+		}
+	}
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds both structs on the C stack
+	classes := make([]uint32, n)
+	count := make([]uint32, 2) // C, rounds
+	room := 64
+	var rep, size []uint32
+	var self, quot []uint8
+	for turn := 0; turn < 2; turn++ {
+		rep, size = make([]uint32, room), make([]uint32, room)
+		self, quot = make([]uint8, P*room), make([]uint8, P*room*room)
+		var rc C.int
+		if v4 {
+			rc = C.clsg_reach_classes_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+				(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+				(*C.uint32_t)(&classes[0]), (*C.uint32_t)(&count[0]), C.uint64_t(room), (*C.uint32_t)(&rep[0]),
+				(*C.uint32_t)(&size[0]), (*C.uint8_t)(&self[0]), (*C.uint8_t)(&quot[0]), nil,
+				(*C.uint32_t)(&count[1]), 0)
+		} else {
+			rc = C.clsg_reach_classes_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+				(*C.uint8_t)(&proto[0]), (*C.uint16_t)(&sport[0]), (*C.uint16_t)(&dport[0]), C.uint32_t(P),
+				(*C.uint32_t)(&classes[0]), (*C.uint32_t)(&count[0]), C.uint64_t(room), (*C.uint32_t)(&rep[0]),
+				(*C.uint32_t)(&size[0]), (*C.uint8_t)(&self[0]), (*C.uint8_t)(&quot[0]), nil,
+				(*C.uint32_t)(&count[1]), 0)
+		}
+		if rc != C.CLS_OK {
+			return nil, en.lastErr()
+		}
+		if int(count[0]) <= room {
+			break
+		}
+		room = int(count[0]) // the per-class outputs were left alone
+	}
+	nc := int(count[0])
+	out.C, out.Rounds = nc, int(count[1])
+	out.Rep, out.Size = make([]uint32, nc), size[:nc]
+	for c := 0; c < nc; c++ {
+		out.Rep[c] = uint32(at[rep[c]])
+	}
+	// (dense in C, whatever the room was)
+	out.Self, out.Quot = self[:P*nc], quot[:P*nc*nc]
+	for k := 0; k < n; k++ {
+		out.Class[at[k]] = int32(classes[k])
+	}
+	return out, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

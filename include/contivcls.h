@@ -51,7 +51,10 @@ extern "C" {
  *    65,536 destination ports: cls_port_range, cls_reach_ports_out) and
  *    cls_port_classes; cls_reach_hops (the multi-hop closure of the matrix:
  *    hop counts, blast radius, exposure: cls_reach_hops_out, CLS_HOPS_NONE)
- *    and the hops_rows option. */
+ *    and the hops_rows option; cls_reach_classes (the endpoints the matrix
+ *    cannot tell apart and the quotient matrix between their classes:
+ *    cls_reach_classes_out, CLS_CLASS_NONE), its device-free twin
+ *    cls_reach_classes_host and the classes_key_bits option. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -202,7 +205,7 @@ int cls_abi_version(void);
  * pair_other_late, pair_o4, pair_map_lds, pair_class, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
- * up to a multiple of 1024 --, hops_rows, debug_modes, debug_conn, debug_floor) for
+ * up to a multiple of 1024 --, hops_rows, classes_key_bits, debug_modes, debug_conn, debug_floor) for
  * later calls; every one keeps verdicts and counters exact.  The library never reads the environment:
  * an engine runs its defaults unless told otherwise here.  CLS_E_INVAL for
  * an unknown key or a malformed value. */
@@ -612,6 +615,90 @@ typedef struct cls_reach_hops_out {
 } cls_reach_hops_out;
 int cls_reach_hops(cls_engine* e, const cls_reach_spec* spec, const uint8_t* matrix,
                    uint32_t max_hops, const cls_reach_hops_out* out, uint32_t flags, void* stream);
+
+/* ---- reachability classes: equivalent endpoints and their quotient matrix --
+ * The summary of a [P][N][N] matrix: the groups of endpoints the policy
+ * cannot tell apart, and the verdict between groups.  Cells are whole bytes.
+ * Endpoints s and t are equivalent iff exchanging s and t leaves the matrix
+ * unchanged; for every probe p:
+ *   M[p,s,d] == M[p,t,d] and M[p,d,s] == M[p,d,t] for all d not in {s, t};
+ *   M[p,s,t] == M[p,t,s];
+ *   M[p,s,s] == M[p,t,t].
+ * Transpositions that are automorphisms generate a group, so this is an
+ * equivalence relation.  The diagonal (self connection, the same-interface
+ * REFLECT short-cut) may differ from the off-diagonal.  Within a class all
+ * diagonal cells are equal and all off-diagonal cells are equal; between two
+ * classes all cells are equal.  So the matrix is exactly reconstructible from
+ *   class[N]       the class of each endpoint
+ *   self[P][C]     the diagonal value of each class
+ *   quot[P][C][C]  the value between classes; quot[p][A][A] is the intra-class
+ *                  off-diagonal value, or CLS_CLASS_NONE for a one-member class
+ * Classes are numbered by ascending smallest member: class[0] == 0, and
+ * rep[c], the first s with class[s] == c, is strictly ascending.  The result
+ * is the coarsest such partition and depends on the matrix alone: not on
+ * reach_tile, the evaluator, scheduling or hashing.
+ * matrix == NULL: the matrix of `spec` is evaluated exactly as
+ * cls_reach_matrix does (the same tiles, bindings snapshotted once for the
+ * whole call, CLS_F_CONN_CLS / CLS_F_FORCE_LINEAR as there).  matrix != NULL:
+ * a matrix of an earlier call, host memory or, with CLS_F_DEVICE, device
+ * memory: only n_endpoints and n_probes of `spec` are read and the evaluator
+ * flags are refused (cls_reach_hops).
+ * How: a fold pass streams every tile and adds, per probe, 64-bit keyed sums
+ * (wrapping, so independent of order) of each row and column off the
+ * diagonal; the host groups endpoints whose sums and diagonals agree (in
+ * every round so far); a verify pass streams the matrix again -- evaluated again, or read
+ * from verdict_out / matrix in device memory -- and checks every cell against
+ * the one value of its (probe, class, class) entry.  Only a collision of keys
+ * can fail it, and then another round with new keys refines the partition, so
+ * the result is exact whatever the keys.  *rounds is the number of rounds
+ * taken: 1 at the full key width.  The classes_key_bits option
+ * (cls_engine_set_option, 0 .. 64, default 64; diagnostics) keeps only the low
+ * bits of the sums in the keys to force collisions; after 16 rounds the call
+ * returns CLS_E_INVAL ("did not converge"), which only that option reaches.
+ * Scratch that cannot be allocated: CLS_E_NOMEM.
+ * Outputs (cls_reach_classes_out): at least one of class_out and n_classes;
+ * the per-class outputs rep_out, size_out, self_out, quot_out hold up to
+ * class_cap classes and are written only when C <= class_cap -- otherwise they
+ * stay untouched, class_out and *n_classes are still written and the call
+ * returns CLS_OK: the caller retries with room.  verdict_out, optional: the
+ * evaluated matrix (with a matrix given: a copy of it).  n_classes, rounds and
+ * sums_out (diagnostics: [P][N][2] row and column sums of the last round) are
+ * HOST memory also with CLS_F_DEVICE, under which the matrix and every other
+ * output are device memory (verdict_out and matrix 16-byte, the u32 arrays
+ * 4-byte aligned) and the device work runs on `stream`.
+ * Unlike the other reach calls this one RETURNS ONLY WHEN THE RESULT IS
+ * COMPLETE, also with CLS_F_DEVICE: the class count and the verify pass's
+ * result decide what is enqueued next.
+ * CLS_E_INVAL, before any device work and with the outputs untouched:
+ * everything cls_reach_hops refuses for the same form, CLS_F_COUNT,
+ * CLS_F_NO_VERDICT, N > 32,768, neither class_out nor n_classes, per-class
+ * outputs with class_cap == 0, a misaligned device pointer.  On a
+ * multi-device engine the call runs on the first device. */
+#define CLS_CLASS_NONE 255u  /* quot[p][A][A] of a one-member class */
+
+typedef struct cls_reach_classes_out {
+    uint32_t* class_out;    /* [N] class of each endpoint */
+    uint32_t* n_classes;    /* HOST word, also with CLS_F_DEVICE: C */
+    uint64_t class_cap;     /* the per-class outputs hold up to class_cap classes */
+    uint32_t* rep_out;      /* [C] smallest member */
+    uint32_t* size_out;     /* [C] members */
+    uint8_t* self_out;      /* [P][C] */
+    uint8_t* quot_out;      /* [P][C][C], dense in C */
+    uint8_t* verdict_out;   /* [P][N][N] optional: the evaluated matrix */
+    uint32_t* rounds;       /* HOST word, diagnostics: rounds taken */
+    uint64_t* sums_out;     /* HOST, diagnostics: [P][N][2] row and column sums of the last round */
+} cls_reach_classes_out;
+int cls_reach_classes(cls_engine* e, const cls_reach_spec* spec, const uint8_t* matrix,
+                      const cls_reach_classes_out* out, uint32_t flags, void* stream);
+/* The device-free twin: the same pipeline on the host over a host matrix,
+ * with the same keys, seeds, grouping and round loop, so that its sums_out
+ * and rounds equal the device call's bit for bit.  key_bits: 0 .. 64 (the
+ * classes_key_bits option; 64 for the exact single round).  Every pointer is
+ * host memory.  CLS_E_INVAL: matrix NULL, N or P zero, above 2^36 cells,
+ * N > 32,768, key_bits > 64, the outputs' refusals above, or no convergence
+ * within 16 rounds; the outputs are then untouched. */
+int cls_reach_classes_host(const uint8_t* matrix, uint32_t n_endpoints, uint32_t n_probes, uint32_t key_bits,
+                           const cls_reach_classes_out* out);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

@@ -368,6 +368,72 @@ static inline int clsg_reach_hops_v16(cls_engine* e, const uint32_t* if_id, cons
     return cls_reach_hops(e, &r, NULL, max_hops, &o, flags, NULL);
 }
 
+/* cls_reach_classes over IPv4 endpoints: the classes of endpoints that the
+ * matrix of clsg_reach_matrix_v4's arguments cannot tell apart, evaluated on
+ * the device.  Host arrays; classes (n) or n_classes is required; rep and
+ * size (class_cap each), self_ (n_probes x class_cap) and quot (n_probes x
+ * class_cap x class_cap) are written, dense in C, only when C <= class_cap;
+ * verdict (n_probes x n x n) and rounds may be NULL.  Returns with the result
+ * complete. */
+static inline int clsg_reach_classes_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                         const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                         uint32_t n_probes, uint32_t* classes, uint32_t* n_classes, uint64_t class_cap,
+                                         uint32_t* rep, uint32_t* size, uint8_t* self_, uint8_t* quot,
+                                         uint8_t* verdict, uint32_t* rounds, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_classes_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.class_out = classes;
+    o.n_classes = n_classes;
+    o.class_cap = class_cap;
+    o.rep_out = rep;
+    o.size_out = size;
+    o.self_out = self_;
+    o.quot_out = quot;
+    o.verdict_out = verdict;
+    o.rounds = rounds;
+    return cls_reach_classes(e, &r, NULL, &o, flags, NULL);
+}
+
+/* cls_reach_classes over 16-byte endpoints (n x 16 network-order bytes). */
+static inline int clsg_reach_classes_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                         const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                         uint32_t n_probes, uint32_t* classes, uint32_t* n_classes, uint64_t class_cap,
+                                         uint32_t* rep, uint32_t* size, uint8_t* self_, uint8_t* quot,
+                                         uint8_t* verdict, uint32_t* rounds, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_classes_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = n_probes;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.class_out = classes;
+    o.n_classes = n_classes;
+    o.class_cap = class_cap;
+    o.rep_out = rep;
+    o.size_out = size;
+    o.self_out = self_;
+    o.quot_out = quot;
+    o.verdict_out = verdict;
+    o.rounds = rounds;
+    return cls_reach_classes(e, &r, NULL, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -70,12 +70,25 @@ against it), and a last line for the matrix form at N = 8192 on a synthetic
 random device matrix of out-degree about 2 (checked against a queue search
 from 64 sources).
 
+--classes measures the reachability classes (cls_reach_classes) instead: per
+--locals value of --diff-locals, N = 2048 endpoints x 4 probes, in one process
+it alternates A as above, B = cls_reach_classes(CLS_F_DEVICE) in the
+evaluating form with every per-class output (two evaluations), the same with a
+device verdict_out (one evaluation, the second pass reads it) and the matrix
+form over A's device matrix, and prints one JSON line per --locals value: the
+medians, B / A, C, the rounds taken, the bytes each leaves to download and,
+once and labelled as CPU, the host alternative (A's verdicts downloaded, then
+the tests' numpy grouping, reach_classes_cases.classes_ref; B is checked
+against it) and the call over that host matrix.  B returns complete, so its
+calls do not overlap; A's are queued back to back.
+
 usage: python tools/reach_bench.py [--af 4|16] [--locals 12] [--endpoints 1024,2048]
            [--tiles 1048576,4194304,16777216] [--iters 9] [--kernel-stats]
        python tools/reach_bench.py --diff [--af 4|16] [--diff-locals 12,64] [--endpoints 2048]
            [--iters 9] [--rounds 7]
        python tools/reach_bench.py --ports [--af 4|16] [--diff-locals 12,64] [--iters 3] [--rounds 5]
            [--kernel-stats]
+       python tools/reach_bench.py --classes [--af 4|16] [--diff-locals 12,64] [--endpoints 2048] [--iters 9]
        python tools/reach_bench.py --hops [--af 4|16] [--diff-locals 12,64] [--endpoints 2048] [--iters 9]
            [--rounds 7] [--kernel-stats]
 """
@@ -533,7 +546,103 @@ def measure_hops_matrix(a):
     return line
 
 
-def kernel_stats(a, n, diff_locals=None, ports=False, hops=False):
+def measure_classes(a, n, n_local):
+    """A / B of cls_reach_matrix and cls_reach_classes on the same engine, and
+    the matrix form over A's device matrix against the host alternative."""
+    import torch
+    import reach_classes_cases as cc
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr, expand_classes
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    bind, by_name, ifs, at, addrs, (pr, sp, dp) = setup(eng, a.af, n_local, n)
+    ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
+    cells = N_PROBES * n * n
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    ep_if = np.ascontiguousarray(ids[at], np.uint32)
+    ep_addr = np.ascontiguousarray(addrs, np.uint8 if a.af == 16 else np.uint32)
+    spec = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                          _ptr(ep_addr) if a.af == 16 else None, N_PROBES, _ptr(pr), _ptr(sp), _ptr(dp))
+    dv = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    dv2 = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    dh = torch.empty((N_PROBES, 4), dtype=torch.int64, device="cuda")
+    da = torch.empty((N_PROBES, n), dtype=torch.int32, device="cuda")
+    cap = 1024
+    classes = torch.empty(n, dtype=torch.int32, device="cuda")
+    reps = torch.empty(cap, dtype=torch.int32, device="cuda")
+    sizes = torch.empty(cap, dtype=torch.int32, device="cuda")
+    self_ = torch.empty(N_PROBES * cap, dtype=torch.uint8, device="cuda")
+    quot = torch.empty(N_PROBES * cap * cap, dtype=torch.uint8, device="cuda")
+    count, rounds = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+
+    def out(verdict):
+        return _abi.ReachClassesOut(_ptr(classes), _ptr(count), cap, _ptr(reps), _ptr(sizes), _ptr(self_), _ptr(quot),
+                                    verdict, _ptr(rounds), None)
+    o_plain, o_verdict = out(None), out(_ptr(dv2))
+
+    def matrix():
+        rc = L.cls_reach_matrix(eng.h, C.byref(spec), _ptr(dv), _ptr(dh), _ptr(da), _abi.F_DEVICE, None)
+        assert rc == 0, L.cls_last_error(eng.h)
+
+    def call(o, m=None):
+        def f():
+            rc = L.cls_reach_classes(eng.h, C.byref(spec), m, C.byref(o), _abi.F_DEVICE, None)
+            assert rc == 0, L.cls_last_error(eng.h)
+        return f
+    b_plain, b_verdict, b_matrix = call(o_plain), call(o_verdict), call(o_plain, _ptr(dv))
+    ta, tb, tv, tm = [], [], [], []
+    for _ in range(a.rounds):
+        ta.append(piped(matrix, a.iters, sync))
+        tb.append(piped(b_plain, a.iters, sync))
+        tv.append(piped(b_verdict, a.iters, sync))
+        tm.append(piped(b_matrix, a.iters, sync))
+    b_plain()
+    k = int(count[0])
+    assert k <= cap and int(rounds[0]) == 1, (k, int(rounds[0]))
+    line = {"metric": "reachability classes: B / A (cls_reach_classes(CLS_F_DEVICE), evaluating form, with classes, "
+                      "reps, sizes, self and quotient against cls_reach_matrix(CLS_F_DEVICE) with verdicts, histogram "
+                      "and allow counts over the same spec, alternated in one process; B returns complete, A is "
+                      "queued back to back)",
+            "af": a.af, "endpoints": n, "probes": N_PROBES, "cells": cells, "local_acls": n_local,
+            "options": a.opt, "iters": a.iters, "rounds": a.rounds, "lib": os.path.basename(_abi.LIB_PATH)}
+    med = lambda t: round(float(np.median(t)), 4)
+    line.update({"A_ms": med(ta), "B_ms": med(tb), "B_over_A": round(med(tb) / med(ta), 4),
+                 "B_with_device_verdict_ms": med(tv), "matrix_form_ms": med(tm),
+                 "A_ms_rounds": [round(x, 4) for x in ta], "B_ms_rounds": [round(x, 4) for x in tb],
+                 "classes": k, "rounds_taken": int(rounds[0]),
+                 "A_bytes_out": cells, "B_bytes_out": n * 4 + k * 8 + N_PROBES * k * (k + 1)})
+    if not a.child:
+        # the host alternative, once: A's matrix downloaded and grouped with numpy; B checked against it
+        matrix()
+        sync()
+        t0 = time.perf_counter()
+        v = dv.cpu().numpy().reshape(N_PROBES, n, n)
+        t1 = time.perf_counter()
+        want = cc.classes_ref(v)
+        t2 = time.perf_counter()
+        got = (classes.cpu().numpy().view(np.uint32), reps.cpu().numpy().view(np.uint32)[:k],
+               sizes.cpu().numpy().view(np.uint32)[:k], self_.cpu().numpy()[:N_PROBES * k].reshape(N_PROBES, k),
+               quot.cpu().numpy()[:N_PROBES * k * k].reshape(N_PROBES, k, k))
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w), "cls_reach_classes differs from classes_ref of cls_reach_matrix's verdicts"
+        assert np.array_equal(expand_classes(got[0], got[3], got[4]), v)
+        b_verdict()
+        assert np.array_equal(dv2.cpu().numpy().reshape(v.shape), v)
+        # the host share of B: the same pipeline on the host over the downloaded matrix, and its grouping alone
+        t3 = time.perf_counter()
+        eng.reach_classes(None, None, None, None, None, matrix=v, class_cap=cap)
+        t4 = time.perf_counter()
+        line.update({"CPU_download_ms": round((t1 - t0) * 1e3, 2), "CPU_classes_ref_ms": round((t2 - t1) * 1e3, 2),
+                     "host_matrix_form_ms": round((t4 - t3) * 1e3, 2),
+                     "CPU_note": "the host alternative, measured once on the CPU: A's %d verdict bytes downloaded, then "
+                                 "the tests' numpy grouping; host_matrix_form_ms: the call over that host matrix" % cells,
+                     "class_sizes_top": sorted(want[2].tolist(), reverse=True)[:8],
+                     "parity": "classes, reps, sizes, self, quotient == classes_ref of A's verdicts; "
+                               "expand_classes == A's verdicts; verdict_out == A's verdicts"})
+    eng.close()
+    return line
+
+
+def kernel_stats(a, n, diff_locals=None, ports=False, hops=False, classes=False):
     """The same measurement in a child under rocprofv3 --kernel-trace --stats
     (a run of its own: the timings above are taken without the profiler):
     average ns per call of the matrix's kernels and of connect_kernel
@@ -542,7 +651,7 @@ def kernel_stats(a, n, diff_locals=None, ports=False, hops=False):
     with tempfile.TemporaryDirectory() as d:
         mode = ["--locals", str(a.locals), "--tiles", str(a.stats_tile), "--cpu-sample", "256"]
         if diff_locals is not None:
-            mode = ["--hops" if hops else "--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
+            mode = ["--classes" if classes else "--hops" if hops else "--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--endpoints", str(n),
                "--iters", str(a.iters)] + mode + [x for o in a.opt for x in ("--opt", o)]
@@ -557,7 +666,8 @@ def kernel_stats(a, n, diff_locals=None, ports=False, hops=False):
             name = row["Name"]
             for key in ("reach_expand4", "reach_expand16", "reach_reduce", "reach_diff_count", "reach_diff_scan",
                         "reach_diff_emit", "reach_ports_expand4", "reach_ports_expand16", "reach_ports_count",
-                        "reach_ports_emit", "reach_adj_fold", "reach_hops_bfs", "connect_kernel"):
+                        "reach_ports_emit", "reach_adj_fold", "reach_hops_bfs", "reach_class_fold", "reach_class_verify",
+                        "connect_kernel"):
                 if key in name:
                     e = out.setdefault(key, {"calls": 0, "total_ns": 0})
                     e["calls"] += int(row["Calls"])
@@ -582,11 +692,22 @@ def main():
     ap.add_argument("--ports", action="store_true", help="A / B of cls_reach_matrix at the class starts and "
                                                          "cls_reach_ports")
     ap.add_argument("--hops", action="store_true", help="A / B of cls_reach_matrix and cls_reach_hops")
-    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports, --hops: alternations of A and B")
+    ap.add_argument("--classes", action="store_true", help="A / B of cls_reach_matrix and cls_reach_classes")
+    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports, --hops, --classes: alternations of A and B")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     a.tiles = [int(x) for x in a.tiles.split(",")]
+    if a.classes:
+        for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
+            for n_local in [int(x) for x in a.diff_locals.split(",")]:
+                line = measure_classes(a, n, n_local)
+                if a.kernel_stats and not a.child:
+                    from vpp_amd import _abi
+                    line["kernel_stats"] = dict(kernel_stats(a, n, n_local, classes=True), sources=_abi.source_hash(),
+                                                note="average per launch over the A and B calls, under the profiler")
+                print(json.dumps(line), flush=True)
+        return
     if a.hops:
         for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
             for n_local in [int(x) for x in a.diff_locals.split(",")]:

@@ -58,7 +58,8 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_batch_upload", "cls_batch_download", "cls_batch_gen_traffic_v4", "cls_batch_gen_traffic_v16",
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
-           "cls_port_classes", "cls_reach_hops"]
+           "cls_port_classes", "cls_reach_hops", "cls_reach_classes",
+           "cls_reach_classes_host"]
 
 
 class ClsRule(C.Structure):
@@ -122,6 +123,19 @@ class ReachHopsOut(C.Structure):
 
 # cls_reach_hops: not reached within max_hops
 HOPS_NONE = 255
+
+
+class ReachClassesOut(C.Structure):
+    """cls_reach_classes_out: the outputs of cls_reach_classes and
+    cls_reach_classes_host; n_classes, rounds and sums_out are host memory."""
+    _fields_ = [("class_out", C.c_void_p), ("n_classes", C.c_void_p), ("class_cap", C.c_uint64),
+                ("rep_out", C.c_void_p), ("size_out", C.c_void_p), ("self_out", C.c_void_p),
+                ("quot_out", C.c_void_p), ("verdict_out", C.c_void_p), ("rounds", C.c_void_p),
+                ("sums_out", C.c_void_p)]
+
+
+# cls_reach_classes: quot[p][A][A] of a one-member class
+CLASS_NONE = 255
 
 # cls_port_range as a numpy structured dtype (16 bytes)
 PORT_RANGE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("port_lo", "<u2"), ("port_hi", "<u2"), ("action", "u1"),
@@ -262,6 +276,8 @@ def bind(path: str, strict: bool = True):
         "cls_reach_ports": (C.c_int, [vp, C.POINTER(ReachSpec), C.POINTER(ReachPortsOut), u32, vp]),
         "cls_port_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
         "cls_reach_hops": (C.c_int, [vp, C.POINTER(ReachSpec), vp, u32, C.POINTER(ReachHopsOut), u32, vp]),
+        "cls_reach_classes": (C.c_int, [vp, C.POINTER(ReachSpec), vp, C.POINTER(ReachClassesOut), u32, vp]),
+        "cls_reach_classes_host": (C.c_int, [vp, u32, u32, u32, C.POINTER(ReachClassesOut)]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

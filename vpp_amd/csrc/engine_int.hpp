@@ -255,6 +255,11 @@ struct cls_engine {
     // bytes, u32 reach and exposed counts, the u64 level histogram, the
     // closure bitmap (a host matrix's tiles use r_base)
     DevBuf r_adj, r_hhops, r_hreach, r_hexposed, r_hlevel, r_hclosure;
+    // cls_reach_classes (reach.cpp), under the same rule: the fold's u64 sums
+    // ([P][N][2]), diagonal bytes and the 8 mask words followed by the verify
+    // pass's flag, the candidate classes, the verify table and a host call's
+    // class_out (a host matrix's tiles use r_base)
+    DevBuf r_csums, r_cdiag, r_cmask, r_ccls, r_ctab;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

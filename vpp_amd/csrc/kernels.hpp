@@ -503,6 +503,23 @@ hipError_t launch_reach_hops_bfs(uint32_t n_ep, uint32_t max_hops, uint32_t rows
                                  uint8_t* hops, uint32_t* reach, uint32_t* exposed, unsigned long long* levels,
                                  unsigned long long* closure, hipStream_t s);
 
+// ---- the reachability classes (k_reach_classes.hip; contivcls.h cls_reach_classes)
+// fold: per cell (p, s, d) off the diagonal of the tile, sums[(p N + s) 2] +=
+// class_g(seed_r, p, d, value) and sums[(p N + d) 2 + 1] += class_g(seed_c, p,
+// s, value) (reach_classes.hpp; 64-bit, wrapping: the values do not depend on
+// the order); diag[p N + s] = the diagonal cell; mask[8]: bit v set for every
+// byte v of the tile.  sums and mask: cleared by the caller before the first
+// tile; all three are the whole matrix's (p counts from the matrix's first
+// probe).  verdict: the tile's n bytes (no alignment needed).
+hipError_t launch_reach_class_fold(const ReachTile& t, const uint8_t* verdict, uint64_t seed_r, uint64_t seed_c,
+                                   unsigned long long* sums, uint8_t* diag, uint32_t* mask, hipStream_t s);
+// verify: every cell of the tile against tab[P][n_classes][n_classes + 1]
+// (reach_classes.hpp: the entry of (p, cls[s], s == d ? n_classes : cls[d]);
+// cleared to empty by the caller before the first tile); *bad |= 1 on a
+// mismatch.  cls: the N candidate classes, each < n_classes.
+hipError_t launch_reach_class_verify(const ReachTile& t, const uint8_t* verdict, const uint32_t* cls, uint32_t n_classes,
+                                     uint32_t* tab, uint32_t* bad, hipStream_t s);
+
 struct TrafficDev {
     uint64_t seed;
     uint32_t pct_pod, pct_dst, pct_port, pct_icmp;

@@ -105,6 +105,14 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
         o.hops_rows = reset ? d.hops_rows : uint32_t(x);
         return true;
     }
+    if (k == "classes_key_bits") {
+        if (!reset && (x < 0 || x > 64)) {
+            why = "option classes_key_bits: 0 .. 64 bits of the row and column sums";
+            return false;
+        }
+        o.classes_key_bits = reset ? d.classes_key_bits : uint32_t(x);
+        return true;
+    }
     if (k == "orient") {
         const std::string v = reset ? "" : value;
         if (!reset && v != "src" && v != "dst") {

@@ -62,6 +62,9 @@ struct Opts {
     uint32_t hops_rows = 0;     // cls_reach_hops: source rows per workgroup of the search, 4, 8 or 16 (0: 4, the
                                 // best of the three measured, profiles/reach_hops_ab_af{4,16}.txt; halved while
                                 // the rows do not fit 64 KiB of LDS)
+    uint32_t classes_key_bits = 64;  // cls_reach_classes, diagnostics: the low bits of the row and column sums kept
+                                     // in the grouping keys, 0 .. 64 (fewer force collisions, so tests reach the
+                                     // round loop; the classes stay exact)
     // ---- batches (fleet.cpp) ----------------------------------------------
     int batch_layout = 2;       // 0 packed, 1 one allocation per field, 2 staggered fields
 };

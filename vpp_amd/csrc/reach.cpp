@@ -21,10 +21,25 @@
 #include "../../include/contivcls.h"
 #include "engine_int.hpp"
 #include "kernels.hpp"
+#include "reach_classes.hpp"
 
 using namespace cls;
 
 constexpr uint64_t kReachMaxCells = 1ull << 36;   // P x N x N of one call
+
+// cls_reach_classes: what one pass over the matrix launches per tile -- the
+// fold into the sums, the diagonal and the mask, or the verify against the
+// table of the candidate classes.
+struct ClassPass {
+    bool verify = false;
+    uint64_t seed_r = 0, seed_c = 0;
+    unsigned long long* sums = nullptr;
+    uint8_t* diag = nullptr;
+    uint32_t* mask = nullptr;
+    const uint32_t* cls = nullptr;
+    uint32_t C = 0;
+    uint32_t *tab = nullptr, *bad = nullptr;
+};
 
 // The call's resolved arguments.
 struct ReachCall {
@@ -49,6 +64,8 @@ struct ReachCall {
     uint32_t* changed_out = nullptr;
     // cls_reach_hops: the adjacency bitmap every tile's ALLOW cells are folded into
     unsigned long long* adj = nullptr;
+    // cls_reach_classes: the pass every tile's cells go through
+    const ClassPass* cpass = nullptr;
     // the chunk counts and their scan: for the records, the total, and a
     // device call's in-place stores (made by the emit launch)
     bool scan() const { return changes || n_changes || (dev && inplace); }
@@ -262,6 +279,12 @@ static int reach_diff_tile(cls_engine* e, const ReachCall& R, const ReachTile& T
     return CLS_OK;
 }
 
+// The tile's launch of a cls_reach_classes pass over its verdict bytes v.
+static hipError_t class_launch(const ClassPass& c, const ReachTile& T, const uint8_t* v, hipStream_t s) {
+    return c.verify ? launch_reach_class_verify(T, v, c.cls, c.C, c.tab, c.bad, s)
+                    : launch_reach_class_fold(T, v, c.seed_r, c.seed_c, c.sums, c.diag, c.mask, s);
+}
+
 // One tile: cells [first, first + n) of the matrix.
 static int reach_tile(cls_engine* e, const ReachCall& R, uint64_t first, uint32_t n) {
     const uint64_t row = first / R.N;                 // (probe, source) row of the first cell
@@ -295,6 +318,7 @@ static int reach_tile(cls_engine* e, const ReachCall& R, uint64_t first, uint32_
         HIPC(e, launch_reach_reduce(T, v, R.hist_out ? e->r_hist.as<unsigned long long>() + 4 * uint64_t(T.p0) : nullptr,
                                     R.allow_out ? e->r_allow.as<uint32_t>() + row : nullptr, e->n_cu, R.s));
     if (R.adj) HIPC(e, launch_reach_adj_fold(T, v, R.adj, e->n_cu, R.s));
+    if (R.cpass) HIPC(e, class_launch(*R.cpass, T, v, R.s));
     if (R.base) {
         const int drc = reach_diff_tile(e, R, T, first, row, v);
         if (drc != CLS_OK) return drc;
@@ -787,5 +811,214 @@ extern "C" int cls_reach_hops(cls_engine* e, const cls_reach_spec* spec, const u
         rc = matrix ? hops_fold_tile(e, C, first, n) : reach_tile(e, R, first, n);
     }
     if (rc == CLS_OK) rc = hops_outputs(e, C);
+    return rc;
+}
+
+// ---- cls_reach_classes: equivalent endpoints and their quotient matrix ----
+// Rounds of two passes over the matrix (k_reach_classes.hip) around the host
+// grouping (reach_classes.cpp): the fold pass -- behind the evaluator in
+// reach_tile, or alone over a matrix in memory -- then class_group, then the
+// verify pass over the candidate.  A pass streams the caller's device matrix
+// or device verdict_out where there is one, a host matrix tile by tile
+// through r_base, and evaluates again otherwise.  The call waits for every
+// pass: the candidate decides the verify table's size, the verify pass's
+// flag whether another round follows.
+
+struct ClassesCall {
+    ReachCall R;
+    const uint8_t* matrix = nullptr;       // null: the matrix of the spec is evaluated
+    bool evaluated = false;                // the evaluating form's first pass has run
+    cls_reach_classes_out o{};
+};
+
+// Checks everything a refusal can depend on: no device work is queued before
+// this returns CLS_OK.
+static int classes_inputs(cls_engine* e, const cls_reach_spec* sp, const uint8_t* matrix,
+                          const cls_reach_classes_out* o, uint32_t flags, void* stream, ClassesCall& C) {
+    ReachCall& R = C.R;
+    if (matrix) {
+        if (!sp->n_endpoints || !sp->n_probes)
+            return fail(e, CLS_E_INVAL, "reach classes without endpoints or probes");
+        if (flags & (CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR))
+            return fail(e, CLS_E_INVAL, "reach classes over a matrix evaluates nothing: no CLS_F_CONN_CLS or "
+                                        "CLS_F_FORCE_LINEAR");
+    } else {
+        const int rc = reach_spec(e, sp, R);
+        if (rc != CLS_OK) return rc;
+        if (!sp->dport) return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
+    }
+    if (flags & (CLS_F_COUNT | CLS_F_NO_VERDICT))
+        return fail(e, CLS_E_INVAL, "reach classes: no CLS_F_COUNT, no CLS_F_NO_VERDICT");
+    if (const char* why = class_refuse(sp->n_endpoints, o)) return fail(e, CLS_E_INVAL, "%s (N %u)", why, sp->n_endpoints);
+    int rc = reach_cells(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    R.dev = flags & CLS_F_DEVICE;
+    if (R.dev && (!aligned(matrix, 16) || !aligned(o->verdict_out, 16) || !aligned(o->class_out, 4) ||
+                  !aligned(o->rep_out, 4) || !aligned(o->size_out, 4)))
+        return fail(e, CLS_E_INVAL, "device reach classes: matrix, verdict_out 16-byte, class_out, rep_out, "
+                                    "size_out 4-byte aligned");
+    if (!matrix) {
+        rc = reach_spec_ifs(e, sp);
+        if (rc != CLS_OK) return rc;
+    }
+    reach_resolve(e, flags, stream, R);
+    C.matrix = matrix;
+    C.o = *o;
+    if (!matrix) R.verdict_out = o->verdict_out;
+    return CLS_OK;
+}
+
+// A scratch buffer of the call; what cannot be allocated is CLS_E_NOMEM.
+static int classes_grow(cls_engine* e, DevBuf& d, size_t bytes) {
+    const hipError_t h = reach_grow(e, d, bytes);
+    if (h == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return fail(e, CLS_E_NOMEM, "reach classes: %zu bytes of device scratch", bytes);
+    }
+    HIPC(e, h);
+    return CLS_OK;
+}
+
+// One pass (R.cpass) over every tile of the matrix.
+static int classes_pass(cls_engine* e, ClassesCall& C) {
+    ReachCall& R = C.R;
+    // the matrix in device memory, where there is one
+    const uint8_t* devmat = !R.dev ? nullptr : C.matrix ? C.matrix : C.evaluated ? C.o.verdict_out : nullptr;
+    // (a host verdict_out is copied out by the first evaluation only)
+    R.verdict_out = C.matrix || (C.evaluated && !R.dev) ? nullptr : C.o.verdict_out;
+    for (uint64_t first = 0; first < R.cells; first += R.tile) {
+        const uint32_t n = uint32_t(std::min(R.tile, R.cells - first));
+        if (!devmat && !C.matrix) {
+            const int rc = reach_tile(e, R, first, n);
+            if (rc != CLS_OK) return rc;
+            continue;
+        }
+        const uint64_t row = first / R.N;
+        const ReachTile T{R.N, uint32_t(row / R.N), uint32_t(row % R.N), uint32_t(first % R.N), n};
+        const uint8_t* v = devmat ? devmat + first : e->r_base.as<uint8_t>();
+        if (!devmat) HIPC(e, hipMemcpyAsync(e->r_base.p, C.matrix + first, n, hipMemcpyHostToDevice, R.s));
+        HIPC(e, class_launch(*R.cpass, T, v, R.s));
+    }
+    if (!C.matrix) C.evaluated = true;
+    return CLS_OK;
+}
+
+// The rounds; on CLS_OK cand holds the verified classes, numbered canonically,
+// and the verify table is in r_ctab.
+static int classes_rounds(cls_engine* e, ClassesCall& C, std::vector<uint32_t>& cand, ClassFold& f, uint32_t& n_classes,
+                          uint32_t& rounds) {
+    ReachCall& R = C.R;
+    const size_t pn = size_t(R.P) * R.N;
+    int rc = classes_grow(e, e->r_csums, pn * 16);
+    if (rc == CLS_OK) rc = classes_grow(e, e->r_cdiag, pn);
+    if (rc == CLS_OK) rc = classes_grow(e, e->r_cmask, 64);
+    if (rc == CLS_OK) rc = classes_grow(e, e->r_ccls, size_t(R.N) * 4);
+    if (rc == CLS_OK && C.matrix && !R.dev) rc = classes_grow(e, e->r_base, size_t(std::min(R.tile, R.cells)));
+    if (rc != CLS_OK) return rc;
+    ClassKeys keys;
+    f.sums.resize(pn * 2);
+    f.diag.resize(pn);
+    uint32_t* mask = e->r_cmask.as<uint32_t>();           // 8 words, then the verify pass's flag
+    ClassPass ps;
+    R.cpass = &ps;
+    for (uint32_t round = 0; round < kClassRounds; ++round) {
+        ps = ClassPass{};
+        ps.seed_r = class_seed(round, 0);
+        ps.seed_c = class_seed(round, 1);
+        ps.sums = e->r_csums.as<unsigned long long>();
+        ps.diag = e->r_cdiag.as<uint8_t>();
+        ps.mask = mask;
+        HIPC(e, hipMemsetAsync(e->r_csums.p, 0, pn * 16, R.s));
+        HIPC(e, hipMemsetAsync(e->r_cmask.p, 0, 64, R.s));
+        rc = classes_pass(e, C);
+        if (rc != CLS_OK) return rc;
+        HIPC(e, hipMemcpyAsync(f.sums.data(), e->r_csums.p, pn * 16, hipMemcpyDeviceToHost, R.s));
+        HIPC(e, hipMemcpyAsync(f.diag.data(), e->r_cdiag.p, pn, hipMemcpyDeviceToHost, R.s));
+        HIPC(e, hipMemcpyAsync(f.mask, e->r_cmask.p, 32, hipMemcpyDeviceToHost, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+        n_classes = class_group(R.N, R.P, e->opts.classes_key_bits, round, f, keys, cand);
+        const size_t tb = class_table_words(R.P, n_classes) * 4;
+        rc = classes_grow(e, e->r_ctab, tb);
+        if (rc != CLS_OK) return rc;
+        HIPC(e, hipMemsetAsync(e->r_ctab.p, 0, tb, R.s));
+        HIPC(e, hipMemcpyAsync(e->r_ccls.p, cand.data(), size_t(R.N) * 4, hipMemcpyHostToDevice, R.s));
+        ps = ClassPass{};
+        ps.verify = true;
+        ps.cls = e->r_ccls.as<uint32_t>();
+        ps.C = n_classes;
+        ps.tab = e->r_ctab.as<uint32_t>();
+        ps.bad = mask + 8;
+        rc = classes_pass(e, C);
+        if (rc != CLS_OK) return rc;
+        uint32_t bad = 0;
+        HIPC(e, hipMemcpyAsync(&bad, mask + 8, 4, hipMemcpyDeviceToHost, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+        rounds = round + 1;
+        if (!bad) return CLS_OK;
+    }
+    return fail(e, CLS_E_INVAL, "reach classes: did not converge in %u rounds (classes_key_bits %u)", kClassRounds,
+                e->opts.classes_key_bits);
+}
+
+// The results to the caller's outputs, device or host.
+static int classes_outputs(cls_engine* e, ClassesCall& C, const std::vector<uint32_t>& cand, const ClassFold& f,
+                           uint32_t n_classes, uint32_t rounds) {
+    const ReachCall& R = C.R;
+    const cls_reach_classes_out& o = C.o;
+    // (a host call's outputs: plain copies)
+    auto put = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        if (!dst || !bytes) return hipSuccess;
+        if (R.dev) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, R.s);
+        std::memcpy(dst, src, bytes);
+        return hipSuccess;
+    };
+    ClassResult r;
+    const bool per_class = (o.rep_out || o.size_out || o.self_out || o.quot_out) && n_classes <= o.class_cap;
+    if (per_class) {
+        std::vector<uint32_t> tab(class_table_words(R.P, n_classes));
+        HIPC(e, hipMemcpyAsync(tab.data(), e->r_ctab.p, tab.size() * 4, hipMemcpyDeviceToHost, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+        class_result(R.N, R.P, n_classes, cand.data(), tab.data(), r);
+        HIPC(e, put(o.rep_out, r.rep.data(), size_t(n_classes) * 4));
+        HIPC(e, put(o.size_out, r.size.data(), size_t(n_classes) * 4));
+        HIPC(e, put(o.self_out, r.self.data(), r.self.size()));
+        HIPC(e, put(o.quot_out, r.quot.data(), r.quot.size()));
+    }
+    HIPC(e, put(o.class_out, cand.data(), size_t(R.N) * 4));
+    if (C.matrix && o.verdict_out && o.verdict_out != C.matrix) {
+        if (R.dev) HIPC(e, hipMemcpyAsync(o.verdict_out, C.matrix, size_t(R.cells), hipMemcpyDeviceToDevice, R.s));
+        else std::memmove(o.verdict_out, C.matrix, size_t(R.cells));
+    }
+    HIPC(e, hipStreamSynchronize(R.s));
+    e->conn_last = nullptr;
+    if (o.n_classes) *o.n_classes = n_classes;
+    if (o.rounds) *o.rounds = rounds;
+    if (o.sums_out) std::memcpy(o.sums_out, f.sums.data(), f.sums.size() * 8);
+    return CLS_OK;
+}
+
+extern "C" int cls_reach_classes(cls_engine* e, const cls_reach_spec* spec, const uint8_t* matrix,
+                                 const cls_reach_classes_out* out, uint32_t flags, void* stream) {
+    if (!e || !spec) return CLS_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    ClassesCall C;
+    ReachCall& R = C.R;
+    int rc = classes_inputs(e, spec, matrix, out, flags, stream, C);
+    if (rc != CLS_OK) return rc;
+    rc = matrix ? reach_follow(e, R) : reach_upload(e, spec, R);
+    if (rc == CLS_OK && !matrix) rc = reach_scratch(e, R);
+    if (rc != CLS_OK) return rc;
+    try {
+        std::vector<uint32_t> cand;
+        ClassFold f;
+        uint32_t n_classes = 0, rounds = 0;
+        rc = classes_rounds(e, C, cand, f, n_classes, rounds);
+        if (rc == CLS_OK) rc = classes_outputs(e, C, cand, f, n_classes, rounds);
+    } catch (const std::bad_alloc&) {
+        rc = fail(e, CLS_E_NOMEM, "reach classes: out of host memory");
+    }
+    // (whatever was enqueued has run, or its stream failed: nothing stream-ordered is left behind)
+    if (rc != CLS_OK && rc != CLS_E_INVAL) (void)hipStreamSynchronize(R.s);
     return rc;
 }

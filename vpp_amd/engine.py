@@ -38,6 +38,20 @@ ReachDiff = collections.namedtuple("ReachDiff", "verdicts changes n_changes tran
 ReachPorts = collections.namedtuple("ReachPorts", "ranges n_ranges runs allow_ports hist n_classes")
 # Engine.reach_hops's result; what was not asked for is None
 ReachHops = collections.namedtuple("ReachHops", "hops reach exposed levels closure")
+# Engine.reach_classes's result; verdict is None unless asked for
+ReachClasses = collections.namedtuple("ReachClasses", "classes reps sizes self_ quotient rounds verdict")
+
+
+def expand_classes(classes, self_, quotient) -> np.ndarray:
+    """The [P, N, N] matrix that Engine.reach_classes summarised: cell (p, s,
+    d) is quotient[p, classes[s], classes[d]] off the diagonal and self_[p,
+    classes[s]] on it."""
+    c = np.asarray(classes).astype(np.int64)
+    q, d = np.asarray(quotient, np.uint8), np.asarray(self_, np.uint8)
+    m = np.ascontiguousarray(q[:, c[:, None], c[None, :]])
+    at = np.arange(len(c))
+    m[:, at, at] = d[:, c]
+    return m
 
 
 def _is_torch(x) -> bool:
@@ -851,6 +865,86 @@ class Engine:
         self._check(_abi.lib().cls_reach_hops(self.h, C.byref(spec), _ptr(matrix), int(max_hops), C.byref(o), flags, s))
         return ReachHops(*res)
 
+    def reach_classes(self, if_ids, addrs, protos, sports, dports, matrix=None, mode: str = "auto",
+                      device: bool = False, verdict: bool = False, class_cap: int = 64, stream=None):
+        """The endpoints the reachability matrix cannot tell apart, and the
+        matrix between their classes (cls_reach_classes): s and t are in one
+        class iff exchanging them leaves the [P, N, N] matrix unchanged.
+        Returns ReachClasses(classes [N] u32, numbered by ascending smallest
+        member; reps [C] u32, each class's smallest member; sizes [C] u32;
+        self_ [P, C] u8, a class's diagonal value; quotient [P, C, C] u8, the
+        value between classes, on its diagonal the value between two members
+        of a class, 255 for a one-member class; rounds, 1 unless the
+        classes_key_bits option forces collisions; verdict, the [P, N, N]
+        matrix when ``verdict``, else None).  expand_classes(classes, self_,
+        quotient) is the matrix again.  ``matrix`` None: the matrix of
+        reach_matrix's arguments is evaluated on the device (mode as there).
+        ``matrix`` a [P, N, N] uint8 array of an earlier call: it is summarised
+        instead, and the other arrays may be None.  ``device``: the results
+        (and a given matrix) are torch GPU tensors, the work runs on
+        ``stream`` (default: the engine's); either way the call returns with
+        the results complete.  ``class_cap``: the classes the first call has
+        room for; with more, the call is made once more with room for all."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        if matrix is None:
+            ids = np.ascontiguousarray(if_ids, np.uint32)
+            a = np.asarray(addrs)
+            v16 = a.ndim == 2
+            a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+            pr, sp = np.ascontiguousarray(protos, np.uint8), np.ascontiguousarray(sports, np.uint16)
+            dp = np.ascontiguousarray(dports, np.uint16)
+            n, p = len(ids), len(pr)
+            if len(a) != n or len(sp) != p or len(dp) != p:
+                raise ClsError("reach classes: N interface ids and addresses, P protocols and ports")
+            spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                                  _ptr(a) if v16 else None, p, _ptr(pr), _ptr(sp), _ptr(dp))
+        else:
+            if _is_torch(matrix):
+                import torch
+                if not device:
+                    raise ClsError("reach classes: a GPU matrix needs the device form (device=True)")
+                ok = matrix.is_cuda and matrix.is_contiguous() and matrix.dtype == torch.uint8
+            else:
+                if device:
+                    raise ClsError("reach classes: the device form takes a GPU matrix")
+                matrix = np.asarray(matrix)
+                ok = matrix.dtype == np.uint8 and matrix.flags.c_contiguous
+            if not ok or matrix.ndim != 3 or matrix.shape[1] != matrix.shape[2]:
+                raise ClsError("reach classes: matrix must be a contiguous uint8 array of shape (P, N, N)")
+            p, n = int(matrix.shape[0]), int(matrix.shape[1])
+            spec = _abi.ReachSpec(_abi.AF_V4, n, None, None, None, p, None, None, None)
+        s = None
+        if device:
+            import torch
+            flags |= _abi.F_DEVICE
+            if stream is not None:
+                s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+            def new(shape, size):
+                return torch.empty(shape, dtype={1: torch.uint8, 4: torch.int32}[size], device="cuda")
+        else:
+            def new(shape, size):
+                return np.zeros(shape, {1: np.uint8, 4: np.uint32}[size])
+        classes = new((n,), 4)
+        v = new((p, n, n), 1) if verdict else None
+        c, rounds = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+        cap = max(1, int(class_cap))
+        for _ in range(2):
+            reps, sizes, self_, quot = new((cap,), 4), new((cap,), 4), new((p, cap), 1), new((p, cap, cap), 1)
+            o = _abi.ReachClassesOut(_ptr(classes), _ptr(c), cap, _ptr(reps), _ptr(sizes), _ptr(self_), _ptr(quot),
+                                     _ptr(v), _ptr(rounds), None)
+            self._check(_abi.lib().cls_reach_classes(self.h, C.byref(spec), _ptr(matrix), C.byref(o), flags, s))
+            if int(c[0]) <= cap:
+                break
+            cap = int(c[0])                              # (the per-class outputs were left alone)
+        k = int(c[0])
+        if k != cap:
+            # the C ABI's arrays are dense in C: the first C classes of each
+            reps, sizes = reps[:k], sizes[:k]
+            self_ = self_.reshape(-1)[:p * k].reshape(p, k)
+            quot = quot.reshape(-1)[:p * k * k].reshape(p, k, k)
+        return ReachClasses(classes, reps, sizes, self_, quot, int(rounds[0]), v)
+
     def stream_floor_conn(self, src_if, dst_if, src, dst, proto, sport, dport, reps: int = 20) -> float:
         """The connection path's HBM floor on a device batch (cls_stream_floor_conn):
         ms per launch of a kernel that reads the same 22 B per IPv4 connection
@@ -1258,6 +1352,34 @@ class ACLEngine:
         at = np.array([e[0] for e in eps])
         out[at[:, None], at[None, :]] = r.hops
         return out
+
+    def connection_classes(self, pods, probes):
+        """The connectivity map of ``pods`` under ``probes`` ((proto, sport,
+        dport) triples): (groups, self_, quotient).  groups: lists of pod ids,
+        the pods that connection_matrix(pods, probes) cannot tell apart --
+        exchanging two pods of a group leaves it unchanged -- ordered by their
+        first pod in ``pods``; self_ [P, C]: a group's pods to themselves;
+        quotient [P, C, C]: the ConnectionAction from any pod of group a to
+        any of group b, on the diagonal between two pods of one group (255 for
+        a group of one).  One engine call (Engine.reach_classes) over the
+        pods' endpoints; with pods the reference fails before testConnection
+        (rows and columns of CONN_FAILURE) the matrix is evaluated first and
+        summarised whole."""
+        n_p = len(probes)
+        if not pods:
+            return [], np.zeros((n_p, 0), np.uint8), np.zeros((n_p, 0, 0), np.uint8)
+        if not probes:                                   # nothing tells the pods apart
+            return [list(pods)], np.zeros((0, 1), np.uint8), np.zeros((0, 1, 1), np.uint8)
+        eps = self._matrix_endpoints(pods)
+        if len(eps) == len(pods):
+            pr = np.array(probes, np.int64).reshape(-1, 3)
+            r = self.engine.reach_classes([e[1] for e in eps], self._matrix_addrs(eps), pr[:, 0], pr[:, 1], pr[:, 2])
+        else:
+            r = self.engine.reach_classes(None, None, None, None, None, matrix=self.connection_matrix(pods, probes))
+        groups = [[] for _ in range(len(r.reps))]
+        for pod, c in zip(pods, r.classes.tolist()):
+            groups[c].append(pod)
+        return groups, r.self_, r.quotient
 
     def connection_ports(self, pods, protocol, src_port):
         """On which destination ports pod s reaches pod d: (ranges, runs),
