@@ -1233,6 +1233,143 @@ func (en *Engine) ReachClasses(pods []podmodel.ID, probes []Probe) (*Classes, er
 	return out, nil
 }
 
+// AddrRange is one maximal range of ReachExternal: for every IPv4 address a in
+// [Lo, Hi] (host order), ConnectionPodToInternet(pods[Pod], a, probe) --
+// Ingress false -- or ConnectionInternetToPod(a, pods[Pod], probe) -- Ingress
+// true -- returns Action, probe being probes[Probe].
+type AddrRange struct {
+	Ingress    bool
+	Probe, Pod int
+	Lo, Hi     uint32
+	Action     aclengine.ConnectionAction
+}
+
+// ReachExternal answers "which remote addresses can this pod talk to, and
+// which can reach it?" for all of IPv4 in one engine call
+// (cls_reach_external): the engine evaluates one representative address per
+// address class of the bound ACLs, through the node's output interface, and
+// returns only the maximal ranges, in (direction, Probe, Pod, Lo) order with
+// egress first, the ranges of one (direction, probe, pod) covering
+// 0..0xFFFFFFFF.  egress, ingress: the directions wanted.  Pods that
+// ConnectionPodToInternet / ConnectionInternetToPod fail before
+// testConnection (unregistered, on another node, without an interface, or an
+// empty node output interface name) stay out of the call: each has the one
+// range 0..0xFFFFFFFF of ConnActionFailure.
+func (en *Engine) ReachExternal(pods []podmodel.ID, probes []Probe, egress, ingress bool) ([]AddrRange, error) {
+	en.Lock()
+	defer en.Unlock()
+	N, P := len(pods), len(probes)
+	var dirs []bool // Ingress of each direction index
+	var mask uint32
+	if egress {
+		dirs, mask = append(dirs, false), mask|1
+	}
+	if ingress {
+		dirs, mask = append(dirs, true), mask|2
+	}
+	if P == 0 || len(dirs) == 0 {
+		return nil, nil
+	}
+	var strs cstrs
+	defer strs.free()
+	extName := en.nodeOutputIf()
+	var at []int // endpoint -> index in pods
+	var ifs []uint32
+	var ips []net.IP
+	inside := make([]int, N) // 1 + the pod's endpoint, 0: left out
+	v4 := true
+	for i, pod := range pods {
+		cfg := en.pods[pod]
+		if cfg == nil || cfg.anotherNode || extName == "" {
+			continue
+		}
+		ifName, ok := en.Contiv.GetIfName(pod.Namespace, pod.Name)
+		if !ok {
+			continue
+		}
+		var v C.uint32_t
+		C.cls_if_id(en.e, strs.add(ifName), &v)
+		at, ifs, ips = append(at, i), append(ifs, uint32(v)), append(ips, cfg.ip)
+		inside[i] = len(at)
+		v4 = v4 && cfg.ip.To4() != nil
+	}
+	n := len(at)
+	var rec []uint32 // 16-byte records: src, probe | dir << 16 | action << 24, lo, hi
+	total := 0
+	if n > 0 {
+		var ext C.uint32_t
+		C.cls_if_id(en.e, strs.add(extName), &ext)
+		a4 := make([]uint32, n)
+		a16 := make([]byte, 16*n)
+		for k := 0; k < n; k++ {
+			if v4 {
+				a := ips[k].To4()
+				a4[k] = uint32(a[0])<<24 | uint32(a[1])<<16 | uint32(a[2])<<8 | uint32(a[3])
+			} else {
+				a := ips[k].To16()
+				if a == nil {
+					return nil, errors.New("connection endpoint is not an IPv4 or IPv6 address")
+				}
+				copy(a16[16*k:], a)
+			}
+		}
+		pr, sp, dp := make([]uint8, P), make([]uint16, P), make([]uint16, P)
+		for k, q := range probes {
+			pr[k], sp[k], dp[k] = uint8(q.Protocol), q.SrcPort, q.DstPort
+		}
+		// every slice goes to the shim as its own pointer (pointer-free Go
+		// memory); the shim builds both structs on the C stack.  The ranges
+		// are counted first, then fetched.
+		var count C.uint64_t
+		for pass := 0; pass < 2; pass++ {
+			var buf unsafe.Pointer
+			if pass == 1 {
+				rec = make([]uint32, 4*int(count))
+				buf = unsafe.Pointer(&rec[0])
+			}
+			var rc C.int
+			if v4 {
+				rc = C.clsg_reach_external_v4(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint32_t)(&a4[0]), C.uint32_t(n),
+					(*C.uint8_t)(&pr[0]), (*C.uint16_t)(&sp[0]), (*C.uint16_t)(&dp[0]), C.uint32_t(P), ext,
+					C.uint32_t(mask), buf, count, &count, nil, nil, nil, nil, 0)
+			} else {
+				rc = C.clsg_reach_external_v16(en.e, (*C.uint32_t)(&ifs[0]), (*C.uint8_t)(&a16[0]), C.uint32_t(n),
+					(*C.uint8_t)(&pr[0]), (*C.uint16_t)(&sp[0]), (*C.uint16_t)(&dp[0]), C.uint32_t(P), ext,
+					C.uint32_t(mask), buf, count, &count, nil, nil, nil, nil, 0)
+			}
+			if rc != C.CLS_OK {
+				return nil, en.lastErr()
+			}
+		}
+		total = len(rec) / 4
+		if int(count) < total { // (the bindings cannot change under the lock)
+			total = int(count)
+		}
+	}
+	// merge, in line order, with the lines of the pods left out (at is
+	// ascending, so the engine's records are in line order over pods too)
+	var out []AddrRange
+	k := 0
+	for _, in := range dirs {
+		for p := 0; p < P; p++ {
+			for s := 0; s < N; s++ {
+				if inside[s] == 0 {
+					out = append(out, AddrRange{Ingress: in, Probe: p, Pod: s, Lo: 0, Hi: 0xFFFFFFFF,
+						Action: aclengine.ConnActionFailure})
+					continue
+				}
+				for k < total && int(rec[4*k]) == inside[s]-1 && int(rec[4*k+1]&0xFFFF) == p &&
+					(rec[4*k+1]>>16&0xFF != 0) == in {
+					out = append(out, AddrRange{Ingress: in, Probe: p, Pod: s, Lo: rec[4*k+2], Hi: rec[4*k+3],
+						Action: aclengine.ConnectionAction(rec[4*k+1] >> 24)})
+					k++
+				}
+			}
+		}
+	}
+	return out, nil
+}
+
 // Table is one compiled ACL on the device (cls_table_put), for batched
 // classification outside the renderer's bindings.
 type Table struct {

@@ -54,7 +54,10 @@ extern "C" {
  *    and the hops_rows option; cls_reach_classes (the endpoints the matrix
  *    cannot tell apart and the quotient matrix between their classes:
  *    cls_reach_classes_out, CLS_CLASS_NONE), its device-free twin
- *    cls_reach_classes_host and the classes_key_bits option. */
+ *    cls_reach_classes_host and the classes_key_bits option;
+ *    cls_reach_external (per-pod remote address ranges over all of IPv4, to
+ *    and from the node's output interface: cls_addr_range,
+ *    cls_reach_ext_out, CLS_EXT_*) and cls_addr_classes. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -699,6 +702,89 @@ int cls_reach_classes(cls_engine* e, const cls_reach_spec* spec, const uint8_t* 
  * within 16 rounds; the outputs are then untouched. */
 int cls_reach_classes_host(const uint8_t* matrix, uint32_t n_endpoints, uint32_t n_probes, uint32_t key_bits,
                            const cls_reach_classes_out* out);
+
+/* ---- reachability external sweep: per-pod address ranges over all of IPv4 --
+ * "Which remote addresses can this pod talk to, and which can reach it?" --
+ * ConnectionPodToInternet / ConnectionInternetToPod (aclengine_mock.go:303-390)
+ * for every IPv4 address at once.  `spec` is as for cls_reach_matrix: N
+ * endpoints, P probes (at most 65,536: a record's probe is 16 bits); ext_if
+ * is the id (cls_if_id) of the node's output interface, which the caller
+ * resolves as ConnectionPodToInternet does.  `dirs` is a set of CLS_EXT_*
+ * bits; D is their number and the directions are indexed in ascending order
+ * of their bit.  For every IPv4 address a
+ *   egress  cell (p, s, a): testConnection(if_id[s], addr[s], ext_if, a,
+ *                                          proto[p], sport[p], dport[p])
+ *   ingress cell (p, s, a): testConnection(ext_if, a, if_id[s], addr[s], ...)
+ * the pods' own range included (the reference does not exclude it); in the
+ * 16-byte layout a is the IPv4-mapped ::ffff:a and endpoints may be native
+ * IPv6.  The bindings are snapshotted once; the same-interface REFLECT
+ * short-cuts apply where if_id[s] == ext_if.
+ * evalACL (:499-524) sees the remote address only in IPNet.Contains tests of
+ * the rules' parsed networks, and a parsed network holds no IPv4 address or
+ * one aligned interval of them, so a cell's ConnectionAction is constant on
+ * every address class: the elementary intervals whose starts are {0}, lo and
+ * hi + 1 <= 2^32 - 1 of every source or destination network of effective
+ * family 4 (strings that fail to parse and family-16 networks contribute
+ * nothing) over the ACLs bound, inbound or outbound, to the endpoints'
+ * interfaces and to ext_if (K classes).  The engine evaluates one
+ * representative per class -- D P N K connections; a line is one (dir, probe,
+ * endpoint), numbered (d P + p) N + s, rows line K + k in tiles of
+ * max(1, reach_tile / K) whole lines -- and compresses them on the device.
+ * Outputs (cls_reach_ext_out), each optional:
+ *   ranges, cap   the first min(*n_ranges, cap) maximal ranges (adjacent
+ *                 classes of equal action merged) in ascending (dir, probe,
+ *                 src, addr_lo) order; the ranges of one line tile
+ *                 [0, 0xFFFFFFFF].  Canonical: they depend on the verdicts
+ *                 alone, not on the classes, reach_tile, the evaluator or the
+ *                 scheduling.  Records at and past that count are not written
+ *   n_ranges      1 word: all ranges, also those beyond cap
+ *   runs_out        [D][P][N]  ranges of the line
+ *   allow_addrs_out [D][P][N]  addresses with CLS_CONN_ALLOW, 0 .. 2^32
+ *   hist_out        [D][P][4]  addresses per ConnectionAction (each row of 4
+ *                              sums to 2^32 N)
+ *   n_classes     HOST word, also with CLS_F_DEVICE: K, written before the
+ *                 call returns
+ * At least one of ranges, n_ranges, runs_out, allow_addrs_out, hist_out must
+ * be given; ranges needs n_ranges and cap >= 1.  Flags: CLS_F_DEVICE -- every
+ * output but n_classes is device memory (ranges 16-byte, n_ranges,
+ * allow_addrs_out and hist_out 8-byte, runs_out 4-byte aligned) and the call
+ * only enqueues on `stream`, ordered like a device connection batch; without
+ * it they are host arrays, filled through engine-owned buffers (no caller
+ * pointer is kept).  CLS_F_CONN_CLS, CLS_F_FORCE_LINEAR: as cls_reach_matrix.
+ * CLS_E_INVAL, before any device work and with the outputs untouched:
+ * everything cls_reach_matrix refuses of `spec`, more than 65,536 probes,
+ * dirs zero or with other bits, an unknown ext_if, `out` NULL, no output,
+ * ranges without n_ranges or with cap 0, a misaligned device pointer,
+ * CLS_F_COUNT or CLS_F_NO_VERDICT (representatives are evaluated: connection
+ * counters would mean nothing), D P N K > 2^36 (K and N in cls_last_error),
+ * K > 2^30.  On a multi-device engine the call runs on the first device. */
+enum { CLS_EXT_EGRESS = 1u, CLS_EXT_INGRESS = 2u };
+
+typedef struct cls_addr_range {  /* 16 bytes */
+    uint32_t src;                /* endpoint index */
+    uint16_t probe;
+    uint8_t dir;                 /* 0 egress (pod -> address), 1 ingress (address -> pod) */
+    uint8_t action;              /* ConnectionAction for every address in [addr_lo, addr_hi] */
+    uint32_t addr_lo, addr_hi;   /* host-order IPv4, inclusive */
+} cls_addr_range;
+
+typedef struct cls_reach_ext_out {
+    cls_addr_range* ranges;
+    uint64_t cap;
+    uint64_t* n_ranges;
+    uint32_t* runs_out;
+    uint64_t* allow_addrs_out;
+    uint64_t* hist_out;
+    uint32_t* n_classes;
+} cls_reach_ext_out;
+int cls_reach_external(cls_engine* e, const cls_reach_spec* spec, uint32_t ext_if, uint32_t dirs,
+                       const cls_reach_ext_out* out, uint32_t flags, void* stream);
+/* The address class starts of one rule list (no device needed): ascending,
+ * lo_out[0] == 0, each in {0}, lo or hi + 1 <= 2^32 - 1 of a source or
+ * destination network whose effective family is 4 (a.b.c.d/n, or an IPv6
+ * string whose masked address is IPv4-mapped).  *n = K; with cap < K only *n
+ * is set.  cls_reach_external uses the sorted union over the bound ACLs. */
+int cls_addr_classes(const cls_rule* rules, uint32_t n_rules, uint32_t* lo_out, uint32_t cap, uint32_t* n);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

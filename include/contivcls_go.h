@@ -434,6 +434,69 @@ static inline int clsg_reach_classes_v16(cls_engine* e, const uint32_t* if_id, c
     return cls_reach_classes(e, &r, NULL, &o, flags, NULL);
 }
 
+/* cls_reach_external over IPv4 endpoints: per-endpoint remote address ranges
+ * over all of IPv4 through the interface ext_if, for p probes and the
+ * directions of dirs (CLS_EXT_EGRESS | CLS_EXT_INGRESS; d of them).  Host
+ * arrays; ranges (cap records of 16 bytes: src as u32, probe as u16, dir and
+ * action as u8, addr_lo and addr_hi as u32; needs n_ranges), n_ranges (1),
+ * runs (d x p x n u32), allow_addrs (d x p x n u64) and hist (d x p x 4 u64)
+ * may each be NULL, but not all; n_classes (1) may be NULL. */
+static inline int clsg_reach_external_v4(cls_engine* e, const uint32_t* if_id, const uint32_t* addr4, uint32_t n,
+                                         const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                         uint32_t p, uint32_t ext_if, uint32_t dirs, void* ranges, uint64_t cap,
+                                         uint64_t* n_ranges, uint32_t* runs, uint64_t* allow_addrs, uint64_t* hist,
+                                         uint32_t* n_classes, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_ext_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V4;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr4 = addr4;
+    r.n_probes = p;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.ranges = (cls_addr_range*)ranges;
+    o.cap = cap;
+    o.n_ranges = n_ranges;
+    o.runs_out = runs;
+    o.allow_addrs_out = allow_addrs;
+    o.hist_out = hist;
+    o.n_classes = n_classes;
+    return cls_reach_external(e, &r, ext_if, dirs, &o, flags, NULL);
+}
+
+/* cls_reach_external over 16-byte endpoints (n x 16 network-order bytes); the
+ * remote addresses are the IPv4-mapped ::ffff:a. */
+static inline int clsg_reach_external_v16(cls_engine* e, const uint32_t* if_id, const uint8_t* addr16, uint32_t n,
+                                          const uint8_t* proto, const uint16_t* sport, const uint16_t* dport,
+                                          uint32_t p, uint32_t ext_if, uint32_t dirs, void* ranges, uint64_t cap,
+                                          uint64_t* n_ranges, uint32_t* runs, uint64_t* allow_addrs, uint64_t* hist,
+                                          uint32_t* n_classes, uint32_t flags) {
+    cls_reach_spec r;
+    cls_reach_ext_out o;
+    memset(&r, 0, sizeof r);
+    r.af = CLS_AF_V16;
+    r.n_endpoints = n;
+    r.if_id = if_id;
+    r.addr16 = addr16;
+    r.n_probes = p;
+    r.proto = proto;
+    r.sport = sport;
+    r.dport = dport;
+    memset(&o, 0, sizeof o);
+    o.ranges = (cls_addr_range*)ranges;
+    o.cap = cap;
+    o.n_ranges = n_ranges;
+    o.runs_out = runs;
+    o.allow_addrs_out = allow_addrs;
+    o.hist_out = hist;
+    o.n_classes = n_classes;
+    return cls_reach_external(e, &r, ext_if, dirs, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

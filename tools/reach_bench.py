@@ -52,6 +52,23 @@ and prints one JSON line: the median ms per call of A and B, B / A, K, the
 ranges and the bytes each leaves to download (B's runs, ALLOW ports and total
 checked against A's verdicts on the device).
 
+--external measures the external sweep (cls_reach_external) instead: per
+--locals value of --diff-locals, N = 2048 endpoints x 4 probes x both
+directions through the first interface (bound to the global table both ways),
+K the address classes of the bound ACLs (Engine.addr_classes); in one process
+it alternates
+
+  A  what a caller can do without the call: cls_connect_batch(CLS_F_DEVICE)
+     over the same D P N K rows prebuilt in HBM, in batches of B's tiles --
+     D P N K verdict bytes that are still to be downloaded and run-length
+     encoded on the host;
+  B  cls_reach_external(CLS_F_DEVICE) with the ranges (cap: their total), the
+     total, the runs and ALLOW addresses per line and the histogram;
+
+and prints one JSON line: the median ms per call of A and B, B / A, K, the
+ranges and the bytes each leaves to download (every output of B checked
+against the run-length encoding of A's verdicts on the device).
+
 --hops measures the hop closure (cls_reach_hops) instead: per --locals value
 of --diff-locals, N = 2048 endpoints (--endpoints) x 4 probes, in one process
 it alternates
@@ -87,6 +104,8 @@ usage: python tools/reach_bench.py [--af 4|16] [--locals 12] [--endpoints 1024,2
        python tools/reach_bench.py --diff [--af 4|16] [--diff-locals 12,64] [--endpoints 2048]
            [--iters 9] [--rounds 7]
        python tools/reach_bench.py --ports [--af 4|16] [--diff-locals 12,64] [--iters 3] [--rounds 5]
+           [--kernel-stats]
+       python tools/reach_bench.py --external [--af 4|16] [--diff-locals 12,64] [--iters 3] [--rounds 5]
            [--kernel-stats]
        python tools/reach_bench.py --classes [--af 4|16] [--diff-locals 12,64] [--endpoints 2048] [--iters 9]
        python tools/reach_bench.py --hops [--af 4|16] [--diff-locals 12,64] [--endpoints 2048] [--iters 9]
@@ -411,6 +430,134 @@ def measure_ports(a, n_local):
     return line
 
 
+def reach_tile_of(a):
+    """The engine's reach_tile under --opt: the default 16 Mi, or the option
+    rounded up to a multiple of 1024 as the engine rounds it."""
+    opts = dict(o.split("=", 1) for o in a.opt)
+    return (int(opts["reach_tile"]) + 1023) & ~1023 if opts.get("reach_tile") else 16 << 20
+
+
+def measure_external(a, n_local):
+    """A / B of cls_connect_batch over the sweep's rows prebuilt in HBM and
+    cls_reach_external."""
+    import torch
+    from vpp_amd import _abi
+    from vpp_amd.engine import Engine, _ptr
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    n, P, D = 2048, N_PROBES, 2
+    bind, by_name, ifs, at, addrs, (pr, sp, dp) = setup(eng, a.af, n_local, n)
+    ext_name = ifs[0]                                   # bound to the global table both ways
+    # the classes over the ACLs of the endpoints' interfaces and the remote one
+    names = sorted({x for i in np.unique(at) for x in bind[ifs[i]] if x is not None} |
+                   {x for x in bind[ext_name] if x is not None})
+    starts = np.unique(np.concatenate([eng.addr_classes(by_name[x]) for x in names])).astype(np.int64)
+    K = len(starts)
+    ids = np.array([eng.if_id(x) for x in ifs], np.uint32)
+    ext = int(eng.if_id(ext_name))
+    lines, rows = D * P * n, D * P * n * K
+    L, sync = _abi.lib(), torch.cuda.synchronize
+    ep_if = np.ascontiguousarray(ids[at], np.uint32)
+    ep_addr = np.ascontiguousarray(addrs, np.uint8 if a.af == 16 else np.uint32)
+    spec = _abi.ReachSpec(a.af, n, _ptr(ep_if), None if a.af == 16 else _ptr(ep_addr),
+                          _ptr(ep_addr) if a.af == 16 else None, P, _ptr(pr), _ptr(sp), _ptr(dp))
+    # A's rows, line-major, built on the device
+    dev = lambda x, t: torch.from_numpy(np.ascontiguousarray(x).view(t)).to("cuda")
+    line = torch.arange(lines, device="cuda")
+    ing = (line // (P * n) == 1)[:, None]
+    pi, si = line // n % P, line % n
+    t_if = dev(ep_if, np.int32)[si][:, None]
+    ext_t = torch.full((1, 1), ext, dtype=torch.int32, device="cuda")
+    full = lambda x: x.expand(lines, K).contiguous().view(-1)
+    src_if, dst_if = full(torch.where(ing, ext_t, t_if)), full(torch.where(ing, t_if, ext_t))
+    if a.af == 16:
+        rem = np.zeros((K, 16), np.uint8)
+        rem[:, 10:12] = 0xFF
+        rem[:, 12:] = starts.astype(">u4").view(np.uint8).reshape(-1, 4)
+        pod, rem, sel = dev(ep_addr, np.uint8)[si][:, None, :], dev(rem, np.uint8)[None], ing[:, :, None]
+        shape = (lines, K, 16)
+    else:
+        pod, rem, sel = dev(ep_addr, np.int32)[si][:, None], dev(starts.astype(np.uint32), np.int32)[None], ing
+        shape = (lines, K)
+    src = torch.where(sel, rem, pod).expand(shape).contiguous().view(-1)
+    dst = torch.where(sel, pod, rem).expand(shape).contiguous().view(-1)
+    t_pr = full(dev(pr, np.uint8)[pi][:, None])
+    t_sp, t_dp = full(dev(sp, np.int16)[pi][:, None]), full(dev(dp, np.int16)[pi][:, None])
+    cv = torch.empty(rows, dtype=torch.uint8, device="cuda")
+    asz = 16 if a.af == 16 else 1
+    per = max(1, reach_tile_of(a) // K) * K              # whole lines, as B's tiles
+    batches = []
+    for f in range(0, rows, per):
+        cnt = min(per, rows - f)
+        sl = (src[f * asz:(f + cnt) * asz], dst[f * asz:(f + cnt) * asz], t_sp[f:f + cnt], t_dp[f:f + cnt],
+              t_pr[f:f + cnt], src_if[f:f + cnt], dst_if[f:f + cnt])
+        if a.af == 16:
+            pk = _abi.PktSoa(_abi.AF_V16, None, None, _ptr(sl[0]), _ptr(sl[1]), _ptr(sl[2]), _ptr(sl[3]), _ptr(sl[4]))
+        else:
+            pk = _abi.PktSoa(_abi.AF_V4, _ptr(sl[0]), _ptr(sl[1]), None, None, _ptr(sl[2]), _ptr(sl[3]), _ptr(sl[4]))
+        batches.append((_abi.ConnSoa(pk, _ptr(sl[5]), _ptr(sl[6])), cnt, cv.data_ptr() + f, sl))
+    total = torch.zeros(1, dtype=torch.int64, device="cuda")
+    runs = torch.empty((D, P, n), dtype=torch.int32, device="cuda")
+    allow = torch.empty((D, P, n), dtype=torch.int64, device="cuda")
+    hist = torch.empty((D, P, 4), dtype=torch.int64, device="cuda")
+    k_out = np.zeros(1, np.uint32)
+    fn = L.cls_reach_external
+    # the ranges are counted first: the cap of the timed calls is their total
+    o = _abi.ReachExtOut(None, 0, _ptr(total), None, None, None, _ptr(k_out))
+    assert fn(eng.h, C.byref(spec), ext, 3, C.byref(o), _abi.F_DEVICE, None) == 0, L.cls_last_error(eng.h)
+    sync()
+    n_ranges = int(total[0])
+    assert int(k_out[0]) == K, (int(k_out[0]), K)
+    rec = torch.empty((n_ranges, 4), dtype=torch.int32, device="cuda")
+    o = _abi.ReachExtOut(_ptr(rec), n_ranges, _ptr(total), _ptr(runs), _ptr(allow), _ptr(hist), _ptr(k_out))
+
+    def connect():
+        for cs, cnt, out, _ in batches:
+            assert L.cls_connect_batch(eng.h, C.byref(cs), cnt, out, _abi.F_DEVICE, None) == 0
+
+    def external():
+        assert fn(eng.h, C.byref(spec), ext, 3, C.byref(o), _abi.F_DEVICE, None) == 0, L.cls_last_error(eng.h)
+    ta, tb = [], []
+    for _ in range(a.rounds):
+        ta.append(piped(connect, a.iters, sync))
+        tb.append(piped(external, a.iters, sync))
+    # parity on the device: A's verdicts, [lines, K], run-length encoded per line
+    sync()
+    v = cv.view(lines, K)
+    first = torch.ones((lines, K), dtype=torch.bool, device="cuda")
+    first[:, 1:] = v[:, 1:] != v[:, :-1]
+    want_runs = first.sum(dim=1)
+    width = torch.from_numpy(np.diff(np.append(starts, 1 << 32))).to("cuda")
+    want_allow = ((v == 2) * width[None]).sum(dim=1)
+    want_hist = torch.stack([((v == x) * width[None]).sum(dim=1).view(D * P, n).sum(dim=1) for x in range(4)], dim=1)
+    assert torch.equal(runs.flatten().to(torch.int64), want_runs), "runs differ from the batch at the class starts"
+    assert torch.equal(allow.flatten(), want_allow) and torch.equal(hist.view(D * P, 4), want_hist)
+    assert int(total[0]) == n_ranges == int(want_runs.sum())
+    li, ki = first.nonzero(as_tuple=True)                # row-major: (line, class) ascending
+    st = torch.from_numpy(starts).to("cuda")
+    last = torch.ones(len(li), dtype=torch.bool, device="cuda")
+    last[:-1] = li[1:] != li[:-1]
+    hi = torch.full((len(li),), (1 << 32) - 1, dtype=torch.int64, device="cuda")
+    hi[:-1] = torch.where(last[:-1], hi[:-1], st[ki[1:]] - 1)
+    want_rec = torch.stack([li % n, (li // n % P) | (li // (P * n)) << 16 | v[li, ki].to(torch.int64) << 24, st[ki], hi],
+                           dim=1)
+    assert torch.equal(rec.to(torch.int64) & 0xFFFFFFFF, want_rec), "records differ from the batch's run lengths"
+    t_a, t_b = float(np.median(ta)), float(np.median(tb))
+    out = {"metric": "external sweep: B / A (cls_reach_external(CLS_F_DEVICE) with ranges, total, runs, ALLOW "
+                     "addresses and histogram against cls_connect_batch(CLS_F_DEVICE) over the same D P N K rows "
+                     "prebuilt in HBM, alternated in one process)",
+           "af": a.af, "endpoints": n, "probes": P, "directions": D, "K": K, "rows": rows, "local_acls": n_local,
+           "acls_bound": len(names), "ext_if": ext_name, "options": a.opt, "iters": a.iters, "rounds": a.rounds,
+           "A_ms": round(t_a, 4), "B_ms": round(t_b, 4), "B_over_A": round(t_b / t_a, 4),
+           "A_ms_rounds": [round(x, 4) for x in ta], "B_ms_rounds": [round(x, 4) for x in tb],
+           "ranges": n_ranges, "ranges_per_line_max": int(want_runs.max()),
+           "A_bytes_out": rows, "A_bytes_in_hbm": rows * (2 * (16 if a.af == 16 else 4) + 13),
+           "B_bytes_out": n_ranges * 16 + lines * 12 + D * P * 32 + 8,
+           "verdict_addresses": hist.view(D * P, 4).sum(dim=0).cpu().numpy().tolist(),
+           "parity": "runs, ALLOW addresses, histogram, total and every record == run-length of A's verdicts"}
+    eng.close()
+    return out
+
+
 HOPS_SYNTH_N = 8192
 
 
@@ -642,7 +789,7 @@ def measure_classes(a, n, n_local):
     return line
 
 
-def kernel_stats(a, n, diff_locals=None, ports=False, hops=False, classes=False):
+def kernel_stats(a, n, diff_locals=None, ports=False, hops=False, classes=False, external=False):
     """The same measurement in a child under rocprofv3 --kernel-trace --stats
     (a run of its own: the timings above are taken without the profiler):
     average ns per call of the matrix's kernels and of connect_kernel
@@ -651,7 +798,7 @@ def kernel_stats(a, n, diff_locals=None, ports=False, hops=False, classes=False)
     with tempfile.TemporaryDirectory() as d:
         mode = ["--locals", str(a.locals), "--tiles", str(a.stats_tile), "--cpu-sample", "256"]
         if diff_locals is not None:
-            mode = ["--classes" if classes else "--hops" if hops else "--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
+            mode = ["--external" if external else "--classes" if classes else "--hops" if hops else "--ports" if ports else "--diff", "--diff-locals", str(diff_locals), "--rounds", str(a.rounds)]
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--endpoints", str(n),
                "--iters", str(a.iters)] + mode + [x for o in a.opt for x in ("--opt", o)]
@@ -667,6 +814,7 @@ def kernel_stats(a, n, diff_locals=None, ports=False, hops=False, classes=False)
             for key in ("reach_expand4", "reach_expand16", "reach_reduce", "reach_diff_count", "reach_diff_scan",
                         "reach_diff_emit", "reach_ports_expand4", "reach_ports_expand16", "reach_ports_count",
                         "reach_ports_emit", "reach_adj_fold", "reach_hops_bfs", "reach_class_fold", "reach_class_verify",
+                        "reach_ext_expand4", "reach_ext_expand16", "reach_ext_count", "reach_ext_emit",
                         "connect_kernel"):
                 if key in name:
                     e = out.setdefault(key, {"calls": 0, "total_ns": 0})
@@ -693,11 +841,32 @@ def main():
                                                          "cls_reach_ports")
     ap.add_argument("--hops", action="store_true", help="A / B of cls_reach_matrix and cls_reach_hops")
     ap.add_argument("--classes", action="store_true", help="A / B of cls_reach_matrix and cls_reach_classes")
-    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports, --hops, --classes: alternations of A and B")
+    ap.add_argument("--external", action="store_true", help="A / B of cls_connect_batch over the sweep's prebuilt rows "
+                                                            "and cls_reach_external")
+    ap.add_argument("--rounds", type=int, default=7, help="--diff, --ports, --hops, --classes, --external: "
+                                                          "alternations of A and B")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     a.tiles = [int(x) for x in a.tiles.split(",")]
+    if a.external:
+        for n_local in [int(x) for x in a.diff_locals.split(",")]:
+            line = measure_external(a, n_local)
+            if a.kernel_stats and not a.child:
+                from vpp_amd import _abi
+                ks = kernel_stats(a, line["endpoints"], n_local, external=True)
+                # per 4 Mi rows: a launch takes a tile of whole lines, about reach_tile rows (the last one fewer)
+                lines = line["rows"] // line["K"]
+                per_launch = line["rows"] / -(-lines // max(1, reach_tile_of(a) // line["K"]))
+                for key, e in ks.items():
+                    if isinstance(e, dict) and "avg_us" in e:
+                        e["us_per_4Mi_rows"] = round(e["avg_us"] * (4 << 20) / per_launch, 2)
+                line["kernel_stats"] = dict(ks, sources=_abi.source_hash(),
+                                            note="average per launch over the A and B calls, under the profiler; "
+                                                 "per 4 Mi rows from the rows of an average launch (reach_diff_scan: "
+                                                 "one workgroup per launch)")
+            print(json.dumps(line), flush=True)
+        return
     if a.classes:
         for n in [int(x) for x in (a.endpoints if a.endpoints != "1024,2048" else "2048").split(",")]:
             for n_local in [int(x) for x in a.diff_locals.split(",")]:

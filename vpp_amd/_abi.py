@@ -59,7 +59,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
            "cls_port_classes", "cls_reach_hops", "cls_reach_classes",
-           "cls_reach_classes_host"]
+           "cls_reach_classes_host", "cls_reach_external", "cls_addr_classes"]
 
 
 class ClsRule(C.Structure):
@@ -133,6 +133,24 @@ class ReachClassesOut(C.Structure):
                 ("quot_out", C.c_void_p), ("verdict_out", C.c_void_p), ("rounds", C.c_void_p),
                 ("sums_out", C.c_void_p)]
 
+
+class AddrRange(C.Structure):
+    """cls_addr_range: one maximal remote address range of a line, 16 bytes."""
+    _fields_ = [("src", C.c_uint32), ("probe", C.c_uint16), ("dir", C.c_uint8), ("action", C.c_uint8),
+                ("addr_lo", C.c_uint32), ("addr_hi", C.c_uint32)]
+
+
+class ReachExtOut(C.Structure):
+    """cls_reach_ext_out: the outputs of cls_reach_external, each optional."""
+    _fields_ = [("ranges", C.c_void_p), ("cap", C.c_uint64), ("n_ranges", C.c_void_p), ("runs_out", C.c_void_p),
+                ("allow_addrs_out", C.c_void_p), ("hist_out", C.c_void_p), ("n_classes", C.c_void_p)]
+
+
+# cls_reach_external's dirs
+EXT_EGRESS, EXT_INGRESS = 1, 2
+# cls_addr_range as a numpy structured dtype (16 bytes)
+ADDR_RANGE = np.dtype([("src", "<u4"), ("probe", "<u2"), ("dir", "u1"), ("action", "u1"), ("addr_lo", "<u4"),
+                       ("addr_hi", "<u4")])
 
 # cls_reach_classes: quot[p][A][A] of a one-member class
 CLASS_NONE = 255
@@ -278,6 +296,8 @@ def bind(path: str, strict: bool = True):
         "cls_reach_hops": (C.c_int, [vp, C.POINTER(ReachSpec), vp, u32, C.POINTER(ReachHopsOut), u32, vp]),
         "cls_reach_classes": (C.c_int, [vp, C.POINTER(ReachSpec), vp, C.POINTER(ReachClassesOut), u32, vp]),
         "cls_reach_classes_host": (C.c_int, [vp, u32, u32, u32, C.POINTER(ReachClassesOut)]),
+        "cls_reach_external": (C.c_int, [vp, C.POINTER(ReachSpec), u32, u32, C.POINTER(ReachExtOut), u32, vp]),
+        "cls_addr_classes": (C.c_int, [vp, u32, vp, u32, C.POINTER(u32)]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

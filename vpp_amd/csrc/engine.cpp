@@ -365,6 +365,7 @@ static int table_compile(cls_engine* e, const char* name, const cls_rule* rules,
     if (rc != CLS_OK) return fail(e, rc, "%s", why.c_str());
     t->conn16 = conn_rules16(s16);
     for (uint32_t p = 0; p < 2; ++p) t->port_lo[p] = port_class_starts(rules, n, p);
+    t->addr_lo = addr_class_starts(rules, n);
     std::string why16;
     q.ok = build_cls16(s16, n, q.img, why16) && build_other4(q.img.sem, n, q.oimg, why16);
     q.why = why16;
@@ -404,6 +405,7 @@ std::shared_ptr<Table> table_clone_host(const Table& s) {
     t->conn4 = s.conn4;
     t->conn16 = s.conn16;
     for (int p = 0; p < 2; ++p) t->port_lo[p] = s.port_lo[p];
+    t->addr_lo = s.addr_lo;
     t->conn_bm = s.conn_bm;
     t->conn_bm_built = s.conn_bm_built;
     t->conn_epoch = s.conn_epoch;

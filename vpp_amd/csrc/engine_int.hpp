@@ -151,6 +151,9 @@ struct Table {
     // cls_reach_ports: the table's port class starts for TCP / UDP
     // (port_class_starts: sorted, unique, the first is 0)
     std::vector<uint16_t> port_lo[2];
+    // cls_reach_external: the table's IPv4 address class starts
+    // (addr_class_starts: sorted, unique, the first is 0)
+    std::vector<uint32_t> addr_lo;
     // the bitmap form of conn4 (conn_bitmap4), built on the first connection
     // batch that wants it; empty when its tables exceed kConnBmMaxWords
     std::vector<uint32_t> conn_bm;
@@ -249,6 +252,8 @@ struct cls_engine {
     // cls_reach_ports (reach.cpp), under the same rule: the u32 runs and ALLOW
     // ports per pair of a host call, the u64 histogram (its tiles, records,
     // chunk counts and total use the matrix's and the diff's buffers)
+    // (cls_reach_external's host call: the same three, by line and by
+    // (direction, probe), its ALLOW addresses u64)
     DevBuf r_runs, r_pallow, r_phist;
     // cls_reach_hops (reach.cpp), under the same rule: the adjacency bitmap
     // (N x W u64 words, cleared per call) and a host call's outputs -- hops
@@ -352,6 +357,10 @@ int upload(cls_engine* e, DevBuf& d, const Cls4Image& im);
 // protocol (TCP, UDP; anything else: {0}) -- 0, and lo16 and hi16 + 1 <= 65535
 // of the rules that carry a destination range for it; sorted and unique
 std::vector<uint16_t> port_class_starts(const cls_rule* rules, uint32_t n, uint32_t proto);
+// reach.cpp (cls_addr_classes): the IPv4 address class starts of a rule list
+// -- 0, and lo and hi + 1 <= 2^32 - 1 of every source or destination network
+// that parse_cidr reduces to family 4; sorted and unique
+std::vector<uint32_t> addr_class_starts(const cls_rule* rules, uint32_t n);
 
 // ---- engine.cpp / connect.cpp internals used by fleet.cpp (the caller holds e->mu)
 int engine_open(int device, cls_engine** out);

@@ -481,6 +481,62 @@ hipError_t launch_reach_ports_emit(const ReachPortsTile& t, const uint8_t* verdi
                                    const unsigned long long* chunk_base, uint4* ranges, unsigned long long cap,
                                    int n_cu, hipStream_t s);
 
+// ---- the external sweep (k_reach_ext.hip; contivcls.h cls_reach_external) --
+// One tile of the sweep: rows [0, n) are the whole lines from (dir index d0,
+// probe p0, endpoint s0) on, line-major -- row i is class i % K of line i / K
+// after the tile's first, lines numbered (d P + p) N + s, n = lines x K <=
+// 2^30.  Every index the kernels form is 32-bit: the host passes runs / allow
+// offset to the tile's first line and hist to its first (dir, probe).  lo: the
+// K class starts (ascending, lo[0] == 0); class k is [lo[k], lo[k + 1] - 1],
+// the last one ends at 2^32 - 1, so a width may be 2^32: widths and their
+// sums are 64-bit.  dir_of: the direction (0 egress, 1 ingress) of dir index
+// 0 and 1.
+struct ReachExtTile {
+    uint32_t n_ep, n_probes;     // N, P
+    uint32_t d0, p0, s0;         // the tile's first line
+    uint32_t K;                  // classes per line
+    uint32_t n;                  // rows in the tile
+    uint32_t dir_of[2];
+    const uint32_t* lo;
+};
+// The tile's rows as a device batch's arrays, in reach_expand's store shape
+// (four rows per lane, the last group padded by repetition): the pod side from
+// the endpoint table, the remote side ext_if and lo[k] (16-byte layout:
+// ::ffff:lo[k]), source and destination by the line's direction, the ports and
+// the protocol of the line's probe (P x {sport | dport << 16, proto}).
+struct ReachExtExpand {
+    const uint32_t* ep_if;
+    const void* ep_addr;
+    const uint2* probe;
+    uint32_t ext_if;
+    uint32_t *src_if, *dst_if;
+    void *src, *dst;
+    uint16_t *sport, *dport;
+    uint8_t* proto;
+};
+hipError_t launch_reach_ext_expand(const ReachExtTile& t, const ReachExtExpand& x, bool k16, int n_cu,
+                                   hipStream_t s);
+// A row starts a range when k == 0 or its verdict byte differs from the row
+// before.  count: chunk_count[chunk] = the starts among the chunk's
+// kReachChunk rows (or null); runs[line'] += the line's starts; allow[line']
+// += width(k) of the rows with CLS_CONN_ALLOW; hist[4 q' + action] += width(k)
+// (q': (dir, probe) after the tile's first); each may be null.  A wave whose
+// 256 rows lie in one line adds its sums once, a workgroup whose chunk lies in
+// one (dir, probe) bins the histogram in LDS and adds each non-zero bin once.
+// verdict: the tile's n bytes, 4-B aligned.
+hipError_t launch_reach_ext_count(const ReachExtTile& t, const uint8_t* verdict, uint32_t* chunk_count,
+                                  uint32_t* runs, unsigned long long* allow, unsigned long long* hist, int n_cu,
+                                  hipStream_t s);
+// emit (behind launch_reach_diff_scan of the chunk counts): the record of the
+// range with index j = chunk_base[chunk] + its start's rank in the chunk
+// (cls_addr_range: {src, probe | dir << 16 | action << 24, addr_lo, addr_hi})
+// while j < cap.  The start row writes the first three words, the range's
+// last row addr_hi at the same index; a range of one row takes one 16-B
+// store.  No range crosses a tile, so every record below min(total, cap) is
+// complete when the launch ends.
+hipError_t launch_reach_ext_emit(const ReachExtTile& t, const uint8_t* verdict, const unsigned long long* chunk_base,
+                                 uint4* ranges, unsigned long long cap, int n_cu, hipStream_t s);
+
 // ---- the hop closure (k_reach_hops.hip; contivcls.h cls_reach_hops) --------
 // fold: the tile's CLS_CONN_ALLOW cells off the diagonal as bits of the
 // adjacency bitmap adj[N][W], W = (N + 63) / 64 -- bit (d & 63) of word

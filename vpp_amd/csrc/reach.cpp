@@ -9,7 +9,8 @@
 // copy to the outputs.  cls_reach_diff is the same call with a baseline: per
 // tile it adds the diff launches (k_reach_diff.hip) behind the reduce launch,
 // and its own outputs at the end.  cls_reach_ports and cls_reach_hops, on the
-// same tile pipeline and scratch, have their sections below.
+// same tile pipeline and scratch, have their sections below, and
+// cls_reach_external behind cls_reach_ports.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 
 #include "../../include/contivcls.h"
 #include "engine_int.hpp"
+#include "goparse.hpp"
 #include "kernels.hpp"
 #include "reach_classes.hpp"
 
@@ -657,6 +659,279 @@ extern "C" int cls_reach_ports(cls_engine* e, const cls_reach_spec* spec, const 
     for (uint64_t pair = 0; rc == CLS_OK && pair < C.pairs; pair += C.per_tile)
         rc = ports_tile(e, C, pair, uint32_t(std::min(C.per_tile, C.pairs - pair)));
     if (rc == CLS_OK) rc = ports_outputs(e, C);
+    return rc;
+}
+
+// ---- cls_reach_external: per-pod address ranges over all of IPv4 ----------
+// The port sweep's twin over the remote address of ConnectionPodToInternet /
+// ConnectionInternetToPod.  One representative address per address class (the
+// parsed networks' interval ends over the bound ACLs) is exact, since evalACL
+// sees the remote address only in IPNet.Contains tests of those networks.
+// The D P N K rows are laid out line-major, row = ((d P + p) N + s) K + k, in
+// tiles of whole lines; per tile the expand launch (k_reach_ext.hip),
+// connect_locked unchanged, then count, reach_diff_scan and emit.
+
+std::vector<uint32_t> addr_class_starts(const cls_rule* rules, uint32_t n) {
+    std::vector<uint32_t> v{0};
+    for (uint32_t i = 0; i < n; ++i)
+        for (const char* str : {rules[i].src_network, rules[i].dst_network}) {
+            if (!str) continue;
+            const Prefix p = parse_cidr(str);
+            if (p.fam != 4 || p.len < 0 || p.len > 32) continue;   // a parse error, or family 16: no IPv4 address
+            const uint32_t lo = uint32_t(p.addr[0]) << 24 | uint32_t(p.addr[1]) << 16 | uint32_t(p.addr[2]) << 8 | p.addr[3];
+            const uint32_t hi = lo | (p.len ? uint32_t((1ull << (32 - p.len)) - 1) : 0xFFFFFFFFu);
+            v.push_back(lo);
+            if (hi != 0xFFFFFFFFu) v.push_back(hi + 1);
+        }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+
+extern "C" int cls_addr_classes(const cls_rule* rules, uint32_t n_rules, uint32_t* lo_out, uint32_t cap,
+                                uint32_t* n) {
+    if (!n || (n_rules && !rules)) return CLS_E_INVAL;
+    const std::vector<uint32_t> v = addr_class_starts(rules, n_rules);
+    *n = uint32_t(v.size());
+    if (lo_out && cap >= v.size()) std::copy(v.begin(), v.end(), lo_out);
+    return CLS_OK;
+}
+
+// The call's resolved arguments: R holds the matrix's (cells = D P N K rows,
+// tile = the rows of a full tile).
+struct ExtCall {
+    ReachCall R;
+    uint32_t K = 0, D = 0, ext_if = 0;
+    uint32_t dir_of[2] = {0, 0};           // the direction (0 egress, 1 ingress) of direction index 0, 1
+    uint64_t lines = 0, per_tile = 0;      // D P N; lines per tile
+    std::vector<uint32_t> lo;              // the K class starts
+    size_t off_lo = 0;                     // in the tables' blob, behind the addresses and the probes
+    cls_reach_ext_out o{};
+    uint64_t cap = 0;                      // min(o.cap, D P N K): no index reaches D P N K
+    bool scan() const { return o.ranges || o.n_ranges; }
+};
+
+// The sorted union of the class starts of the tables bound, inbound or
+// outbound, to any interface of the endpoints or to ext_if.
+static void ext_classes(cls_engine* e, const cls_reach_spec* sp, ExtCall& C) {
+    C.lo.assign(1, 0);
+    std::vector<uint8_t> seen_if(e->if_acl.size(), 0);
+    std::vector<int32_t> tids;
+    const auto add_if = [&](uint32_t id) {
+        if (seen_if[id]) return;
+        seen_if[id] = 1;
+        tids.push_back(e->if_acl[id].first);
+        tids.push_back(e->if_acl[id].second);
+    };
+    add_if(C.ext_if);
+    for (uint32_t i = 0; i < sp->n_endpoints; ++i) add_if(sp->if_id[i]);
+    std::sort(tids.begin(), tids.end());
+    tids.erase(std::unique(tids.begin(), tids.end()), tids.end());
+    for (int32_t tid : tids) {
+        if (tid < 0) continue;
+        const auto it = e->tables.find(uint32_t(tid));
+        if (it == e->tables.end()) continue;
+        const std::vector<uint32_t>& v = it->second->addr_lo;
+        C.lo.insert(C.lo.end(), v.begin(), v.end());
+    }
+    std::sort(C.lo.begin(), C.lo.end());
+    C.lo.erase(std::unique(C.lo.begin(), C.lo.end()), C.lo.end());
+}
+
+// Checks everything a refusal can depend on: no device work is queued before
+// this returns CLS_OK.
+static int ext_inputs(cls_engine* e, const cls_reach_spec* sp, uint32_t ext_if, uint32_t dirs,
+                      const cls_reach_ext_out* o, uint32_t flags, void* stream, ExtCall& C) {
+    ReachCall& R = C.R;
+    int rc = reach_spec(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    if (!sp->dport) return fail(e, CLS_E_INVAL, "missing reach matrix arrays");
+    if (!dirs || (dirs & ~uint32_t(CLS_EXT_EGRESS | CLS_EXT_INGRESS)))
+        return fail(e, CLS_E_INVAL, "reach external: dirs is CLS_EXT_EGRESS, CLS_EXT_INGRESS or both");
+    if (flags & (CLS_F_COUNT | CLS_F_NO_VERDICT))
+        return fail(e, CLS_E_INVAL, "reach external evaluates representatives: no CLS_F_COUNT, no CLS_F_NO_VERDICT");
+    if (!o->ranges && !o->n_ranges && !o->runs_out && !o->allow_addrs_out && !o->hist_out)
+        return fail(e, CLS_E_INVAL, "reach external without ranges, n_ranges, runs_out, allow_addrs_out or hist_out");
+    if (o->ranges && !o->n_ranges) return fail(e, CLS_E_INVAL, "reach external: ranges without n_ranges");
+    if (o->ranges && !o->cap) return fail(e, CLS_E_INVAL, "reach external: ranges with cap 0");
+    rc = reach_cells(e, sp, R);
+    if (rc != CLS_OK) return rc;
+    if (R.P > 65536) return fail(e, CLS_E_INVAL, "reach external above 65536 probes (P %u)", R.P);
+    R.dev = flags & CLS_F_DEVICE;
+    if (R.dev && (!aligned(o->ranges, 16) || !aligned(o->n_ranges, 8) || !aligned(o->allow_addrs_out, 8) ||
+                  !aligned(o->hist_out, 8) || !aligned(o->runs_out, 4)))
+        return fail(e, CLS_E_INVAL, "device reach external: ranges 16-byte, n_ranges, allow_addrs_out, hist_out "
+                                    "8-byte, runs_out 4-byte aligned");
+    rc = reach_spec_ifs(e, sp);
+    if (rc != CLS_OK) return rc;
+    if (ext_if >= e->if_acl.size()) return fail(e, CLS_E_INVAL, "reach external: unknown interface id ext_if %u", ext_if);
+    C.ext_if = ext_if;
+    if (dirs & CLS_EXT_EGRESS) C.dir_of[C.D++] = 0;
+    if (dirs & CLS_EXT_INGRESS) C.dir_of[C.D++] = 1;
+    ext_classes(e, sp, C);
+    if (C.lo.size() > (1u << 30)) return fail(e, CLS_E_INVAL, "reach external above 2^30 classes (K %zu)", C.lo.size());
+    C.K = uint32_t(C.lo.size());
+    C.lines = uint64_t(C.D) * R.P * R.N;              // <= 2^35
+    if (C.lines > kReachMaxCells / C.K)
+        return fail(e, CLS_E_INVAL, "reach external above 2^36 rows (K %u classes x N %u endpoints x %u probes x %u "
+                                    "directions)", C.K, R.N, R.P, C.D);
+    R.cells = C.lines * C.K;
+    // whole lines per tile (one when K exceeds reach_tile): no range crosses a tile
+    C.per_tile = std::max<uint64_t>(1, e->opts.reach_tile / C.K);
+    R.tile = C.per_tile * C.K;                        // <= max(reach_tile, K) <= 2^30
+    R.mode = flags & (CLS_F_CONN_CLS | CLS_F_FORCE_LINEAR);
+    R.s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    C.o = *o;
+    C.cap = o->ranges ? std::min(o->cap, R.cells) : 0;
+    R.off_addr = (size_t(R.N) * 4 + 15) & ~size_t(15);
+    R.off_probe = (R.off_addr + size_t(R.N) * (R.k16 ? 16 : 4) + 15) & ~size_t(15);
+    C.off_lo = (R.off_probe + size_t(R.P) * sizeof(uint2) + 15) & ~size_t(15);
+    R.tab_bytes = C.off_lo + ((size_t(C.K) * 4 + 15) & ~size_t(15));
+    if (o->n_classes) *o->n_classes = C.K;
+    return CLS_OK;
+}
+
+// The endpoint and probe tables with the class starts behind them.
+static int ext_upload(cls_engine* e, const cls_reach_spec* sp, const ExtCall& C) {
+    const ReachCall& R = C.R;
+    std::vector<uint8_t> tab(R.tab_bytes, 0);
+    std::memcpy(tab.data(), sp->if_id, size_t(R.N) * 4);
+    std::memcpy(tab.data() + R.off_addr, R.k16 ? static_cast<const void*>(sp->addr16) : sp->addr4,
+                size_t(R.N) * (R.k16 ? 16 : 4));
+    uint2* pr = reinterpret_cast<uint2*>(tab.data() + R.off_probe);
+    for (uint32_t p = 0; p < R.P; ++p) pr[p] = uint2{uint32_t(sp->sport[p]) | uint32_t(sp->dport[p]) << 16, sp->proto[p]};
+    std::memcpy(tab.data() + C.off_lo, C.lo.data(), size_t(C.K) * 4);
+    return reach_upload_tab(e, R, tab);
+}
+
+// Where the per-line sums and the histogram accumulate: the caller's device
+// memory, or the engine's for a host call.
+static uint32_t* ext_runs(cls_engine* e, const ExtCall& C) {
+    return !C.o.runs_out ? nullptr : C.R.dev ? C.o.runs_out : e->r_runs.as<uint32_t>();
+}
+static unsigned long long* ext_allow(cls_engine* e, const ExtCall& C) {
+    return !C.o.allow_addrs_out ? nullptr
+           : C.R.dev            ? reinterpret_cast<unsigned long long*>(C.o.allow_addrs_out)
+                                : e->r_pallow.as<unsigned long long>();
+}
+static unsigned long long* ext_hist(cls_engine* e, const ExtCall& C) {
+    return !C.o.hist_out ? nullptr
+           : C.R.dev     ? reinterpret_cast<unsigned long long*>(C.o.hist_out)
+                         : e->r_phist.as<unsigned long long>();
+}
+
+// Beyond reach_scratch: a host call's records (cap of them) and sums, the
+// tile's chunk counts and first indices, the running total; all cleared.
+static int ext_scratch(cls_engine* e, const ExtCall& C) {
+    const ReachCall& R = C.R;
+    const size_t n = size_t(std::min(R.tile, R.cells)), hb = size_t(C.D) * R.P * 4 * 8;
+    if (!R.dev) {
+        if (C.o.ranges) HIPC(e, reach_grow(e, e->r_changes, size_t(C.cap) * sizeof(cls_addr_range)));
+        if (C.o.runs_out) HIPC(e, reach_grow(e, e->r_runs, size_t(C.lines) * 4));
+        if (C.o.allow_addrs_out) HIPC(e, reach_grow(e, e->r_pallow, size_t(C.lines) * 8));
+        if (C.o.hist_out) HIPC(e, reach_grow(e, e->r_phist, hb));
+    }
+    if (C.scan()) {
+        const size_t chunks = (n + kReachChunk - 1) / kReachChunk;
+        HIPC(e, reach_grow(e, e->r_dcount, chunks * 4));
+        HIPC(e, reach_grow(e, e->r_dbase, chunks * 8));
+        HIPC(e, reach_grow(e, e->r_dtotal, 8));
+        HIPC(e, hipMemsetAsync(e->r_dtotal.p, 0, 8, R.s));
+    }
+    if (uint32_t* p = ext_runs(e, C)) HIPC(e, hipMemsetAsync(p, 0, size_t(C.lines) * 4, R.s));
+    if (unsigned long long* p = ext_allow(e, C)) HIPC(e, hipMemsetAsync(p, 0, size_t(C.lines) * 8, R.s));
+    if (unsigned long long* p = ext_hist(e, C)) HIPC(e, hipMemsetAsync(p, 0, hb, R.s));
+    return CLS_OK;
+}
+
+// One tile: the nl whole lines from `line` on.
+static int ext_tile(cls_engine* e, const ExtCall& C, uint64_t line, uint32_t nl) {
+    const ReachCall& R = C.R;
+    const uint8_t* tab = e->r_tab.as<uint8_t>();
+    const uint32_t n = nl * C.K;
+    const uint64_t q = line / R.N;                    // the first line's (dir, probe)
+    const ReachExtTile T{R.N, R.P, uint32_t(q / R.P), uint32_t(q % R.P), uint32_t(line % R.N), C.K, n,
+                         {C.dir_of[0], C.dir_of[1]}, reinterpret_cast<const uint32_t*>(tab + C.off_lo)};
+    ReachExtExpand X{};
+    X.ep_if = reinterpret_cast<const uint32_t*>(tab);
+    X.ep_addr = tab + R.off_addr;
+    X.probe = reinterpret_cast<const uint2*>(tab + R.off_probe);
+    X.ext_if = C.ext_if;
+    X.src_if = e->r_sif.as<uint32_t>(); X.dst_if = e->r_dif.as<uint32_t>();
+    X.src = e->r_src.p; X.dst = e->r_dst.p;
+    X.sport = e->r_sport.as<uint16_t>(); X.dport = e->r_dport.as<uint16_t>();
+    X.proto = e->r_proto.as<uint8_t>();
+    HIPC(e, launch_reach_ext_expand(T, X, R.k16, e->n_cu, R.s));
+    // the evaluator, unchanged: a device batch over the expanded arrays
+    cls_conn_soa c{};
+    c.pkt.af = R.k16 ? CLS_AF_V16 : CLS_AF_V4;
+    if (R.k16) {
+        c.pkt.src16 = e->r_src.as<uint8_t>(); c.pkt.dst16 = e->r_dst.as<uint8_t>();
+    } else {
+        c.pkt.src4 = e->r_src.as<uint32_t>(); c.pkt.dst4 = e->r_dst.as<uint32_t>();
+    }
+    c.pkt.sport = X.sport; c.pkt.dport = X.dport; c.pkt.proto = X.proto;
+    c.src_if = X.src_if; c.dst_if = X.dst_if;
+    const uint8_t* v = e->r_verdict.as<uint8_t>();
+    const int rc = connect_locked(e, &c, n, e->r_verdict.as<uint8_t>(), CLS_F_DEVICE | R.mode, R.s, false);
+    if (rc != CLS_OK) return rc;
+    uint32_t* runs = ext_runs(e, C);
+    unsigned long long* allow = ext_allow(e, C);
+    unsigned long long* hist = ext_hist(e, C);
+    uint32_t* count = C.scan() ? e->r_dcount.as<uint32_t>() : nullptr;
+    HIPC(e, launch_reach_ext_count(T, v, count, runs ? runs + line : nullptr, allow ? allow + line : nullptr,
+                                   hist ? hist + 4 * q : nullptr, e->n_cu, R.s));
+    if (!C.scan()) return CLS_OK;
+    unsigned long long* at = e->r_dbase.as<unsigned long long>();
+    HIPC(e, launch_reach_diff_scan((n + kReachChunk - 1) / kReachChunk, count, at,
+                                   e->r_dtotal.as<unsigned long long>(), R.s));
+    cls_addr_range* rec = !C.o.ranges ? nullptr : R.dev ? C.o.ranges : e->r_changes.as<cls_addr_range>();
+    HIPC(e, launch_reach_ext_emit(T, v, at, reinterpret_cast<uint4*>(rec), C.cap, e->n_cu, R.s));
+    return CLS_OK;
+}
+
+// A host call's sums, total and records through the engine's buffers (it
+// waits for the total and copies that many records, none past them); a device
+// call's total.  A device call is stream-ordered (conn_last).
+static int ext_outputs(cls_engine* e, const ExtCall& C) {
+    const ReachCall& R = C.R;
+    if (R.dev) {
+        if (C.o.n_ranges) HIPC(e, hipMemcpyAsync(C.o.n_ranges, e->r_dtotal.p, 8, hipMemcpyDeviceToDevice, R.s));
+        e->conn_last = R.s;
+        return CLS_OK;
+    }
+    const hipMemcpyKind kind = hipMemcpyDeviceToHost;
+    if (C.o.runs_out) HIPC(e, hipMemcpyAsync(C.o.runs_out, e->r_runs.p, size_t(C.lines) * 4, kind, R.s));
+    if (C.o.allow_addrs_out) HIPC(e, hipMemcpyAsync(C.o.allow_addrs_out, e->r_pallow.p, size_t(C.lines) * 8, kind, R.s));
+    if (C.o.hist_out) HIPC(e, hipMemcpyAsync(C.o.hist_out, e->r_phist.p, size_t(C.D) * R.P * 4 * 8, kind, R.s));
+    uint64_t total = 0;
+    if (C.o.n_ranges) HIPC(e, hipMemcpyAsync(&total, e->r_dtotal.p, 8, kind, R.s));
+    HIPC(e, hipStreamSynchronize(R.s));
+    const uint64_t n = std::min(total, C.cap);
+    if (C.o.ranges && n) {
+        HIPC(e, hipMemcpyAsync(C.o.ranges, e->r_changes.p, size_t(n) * sizeof(cls_addr_range), kind, R.s));
+        HIPC(e, hipStreamSynchronize(R.s));
+    }
+    if (C.o.n_ranges) *C.o.n_ranges = total;
+    e->conn_last = nullptr;
+    return CLS_OK;
+}
+
+extern "C" int cls_reach_external(cls_engine* e, const cls_reach_spec* spec, uint32_t ext_if, uint32_t dirs,
+                                  const cls_reach_ext_out* out, uint32_t flags, void* stream) {
+    if (!e || !spec) return CLS_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const DeviceGuard dg;        // the caller's device again on return
+    if (!out) return fail(e, CLS_E_INVAL, "reach external without outputs");
+    ExtCall C;
+    int rc = ext_inputs(e, spec, ext_if, dirs, out, flags, stream, C);
+    if (rc != CLS_OK) return rc;
+    rc = ext_upload(e, spec, C);
+    if (rc == CLS_OK) rc = reach_scratch(e, C.R);
+    if (rc == CLS_OK) rc = ext_scratch(e, C);
+    for (uint64_t line = 0; rc == CLS_OK && line < C.lines; line += C.per_tile)
+        rc = ext_tile(e, C, line, uint32_t(std::min(C.per_tile, C.lines - line)));
+    if (rc == CLS_OK) rc = ext_outputs(e, C);
     return rc;
 }
 

@@ -784,6 +784,109 @@ class Engine:
         self._check(fn(self.h, C.byref(spec), C.byref(o), flags | _abi.F_DEVICE, s))
         return ReachPorts(*res, int(k[0]))
 
+    @staticmethod
+    def addr_classes(rules) -> np.ndarray:
+        """The IPv4 address class starts of one rule list (cls_addr_classes;
+        no device): ascending u32, the first 0 -- 0 and the lo / hi + 1 of the
+        source and destination networks whose effective family is 4."""
+        cr = rules if isinstance(rules, _abi.CRules) else _abi.CRules(rules)
+        n = C.c_uint32(0)
+        rc = _abi.lib().cls_addr_classes(cr.ptr(), cr.n, None, 0, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_addr_classes: rc=%d" % rc)
+        lo = np.zeros(n.value, np.uint32)
+        rc = _abi.lib().cls_addr_classes(cr.ptr(), cr.n, _ptr(lo), n.value, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_addr_classes: rc=%d" % rc)
+        return lo
+
+    def reach_external(self, if_ids, addrs, protos, sports, dports, ext_if: int, dirs=("egress", "ingress"),
+                       cap=None, mode: str = "auto", out=None, stream=None):
+        """The external sweep (cls_reach_external): which remote IPv4
+        addresses, of all 2^32, endpoint s reaches ("egress") and which reach
+        it ("ingress") through the node's output interface ``ext_if`` (an
+        interface id) -- ``if_ids``, ``addrs`` and the P probes as
+        reach_matrix; ``dirs`` names the D directions wanted, indexed egress
+        before ingress.  Returns a dict: ranges, the maximal (src, probe, dir,
+        action, addr_lo, addr_hi) ranges in (dir, probe, src, addr_lo) order;
+        total, all of them, also beyond ``cap``; runs [D, P, N] u32, ranges
+        per line; allow_addrs [D, P, N] u64, addresses with CONN_ALLOW; hist
+        [D, P, 4] u64, addresses per ConnectionAction; n_classes, the address
+        classes K evaluated per line.
+        out None: the host form -- numpy results, ranges a structured array
+        (_abi.ADDR_RANGE) cut to min(total, cap), total an int; cap None keeps
+        all ranges (a first call counts them), cap 0 asks for none.
+        out a sequence (ranges, total, runs, allow_addrs, hist) of contiguous
+        torch GPU tensors (None allocates one): the device form -- ranges an
+        int32 [cap, 4] tensor of (src, probe | dir << 16 | action << 24,
+        addr_lo, addr_hi) rows of which the first min(total, cap) are written
+        (cap None: its rows), total int64 [1], allow_addrs and hist int64; the
+        call only enqueues on ``stream`` (default: the engine's).  n_classes
+        is an int either way."""
+        flags = {"auto": 0, "classifier": _abi.F_CONN_CLS, "linear": _abi.F_FORCE_LINEAR}[mode]
+        bits = {"egress": _abi.EXT_EGRESS, "ingress": _abi.EXT_INGRESS}
+        dmask = 0
+        for x in ([dirs] if isinstance(dirs, str) else dirs):
+            if x not in bits:
+                raise ClsError("reach external: dirs names 'egress' and / or 'ingress'")
+            dmask |= bits[x]
+        nd = bin(dmask).count("1")
+        ids = np.ascontiguousarray(if_ids, np.uint32)
+        a = np.asarray(addrs)
+        v16 = a.ndim == 2
+        a = np.ascontiguousarray(a, np.uint8).reshape(-1, 16) if v16 else np.ascontiguousarray(a, np.uint32)
+        pr, sp = np.ascontiguousarray(protos, np.uint8), np.ascontiguousarray(sports, np.uint16)
+        dp = np.ascontiguousarray(dports, np.uint16)
+        n, p = len(ids), len(pr)
+        if len(a) != n or len(sp) != p or len(dp) != p:
+            raise ClsError("reach external: N interface ids and addresses, P protocols and ports")
+        spec = _abi.ReachSpec(_abi.AF_V16 if v16 else _abi.AF_V4, n, _ptr(ids), None if v16 else _ptr(a),
+                              _ptr(a) if v16 else None, p, _ptr(pr), _ptr(sp), _ptr(dp))
+        k = np.zeros(1, np.uint32)
+        fn = _abi.lib().cls_reach_external
+        names = ("ranges", "total", "runs", "allow_addrs", "hist")
+        if out is None:
+            total = np.zeros(1, np.uint64)
+            if cap is None:
+                o = _abi.ReachExtOut(None, 0, _ptr(total), None, None, None, _ptr(k))
+                self._check(fn(self.h, C.byref(spec), int(ext_if), dmask, C.byref(o), flags, None))
+                cap = int(total[0])
+            cap = int(cap)
+            rec = np.zeros(cap, _abi.ADDR_RANGE) if cap > 0 else None
+            runs, allow = np.zeros((nd, p, n), np.uint32), np.zeros((nd, p, n), np.uint64)
+            hist = np.zeros((nd, p, 4), np.uint64)
+            o = _abi.ReachExtOut(_ptr(rec), cap, _ptr(total), _ptr(runs), _ptr(allow), _ptr(hist), _ptr(k))
+            self._check(fn(self.h, C.byref(spec), int(ext_if), dmask, C.byref(o), flags, None))
+            if rec is not None:
+                rec = rec[:min(int(total[0]), cap)]
+            return dict(zip(names, (rec, int(total[0]), runs, allow, hist)), n_classes=int(k[0]))
+        import torch
+        res = list(out)
+        if len(res) != 5:
+            raise ClsError("reach external: out is (ranges, total, runs, allow_addrs, hist)")
+        if cap is None:
+            if res[0] is None:
+                raise ClsError("reach external: the device form needs cap or a ranges tensor")
+            cap = res[0].shape[0]
+        cap = int(cap)
+        shapes = ((cap, 4), (1,), (nd, p, n), (nd, p, n), (nd, p, 4))
+        kinds = ((torch.int32, 4), (torch.int64, 8), (torch.int32, 4), (torch.int64, 8), (torch.int64, 8))
+        for i, (sh, (dt, sz)) in enumerate(zip(shapes, kinds)):
+            if i == 0 and cap == 0:
+                res[0] = None
+            elif res[i] is None:
+                res[i] = torch.empty(sh, dtype=dt, device="cuda")
+            elif not (_is_torch(res[i]) and res[i].is_cuda and res[i].is_contiguous() and
+                      res[i].element_size() == sz and tuple(res[i].shape) == sh):
+                raise ClsError("reach external: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                               "elements" % (i, sh, sz))
+        s = None
+        if stream is not None:
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.ReachExtOut(_ptr(res[0]), cap, _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), _ptr(res[4]), _ptr(k))
+        self._check(fn(self.h, C.byref(spec), int(ext_if), dmask, C.byref(o), flags | _abi.F_DEVICE, s))
+        return dict(zip(names, res), n_classes=int(k[0]))
+
     def reach_hops(self, if_ids, addrs, protos, sports, dports, max_hops: int = 0, matrix=None, mode: str = "auto",
                    count: bool = False, hops: bool = True, reach: bool = True, exposed: bool = True,
                    levels: bool = True, closure: bool = False, out=None, stream=None):
@@ -1408,6 +1511,50 @@ class ACLEngine:
                 for lo, hi, act in per.get((s, d), [(0, 65535, CONN_FAILURE)]):
                     ranges.append((s, d, lo, hi, act))
         return ranges, runs
+
+    def connection_external(self, pods, probes, dirs=("egress", "ingress")):
+        """Which remote IPv4 addresses each pod reaches and which reach it: a
+        dict (dir, probe index, pod index) -> the list of maximal (addr_lo,
+        addr_hi, action) ranges, ascending and covering 0 .. 0xFFFFFFFF, such
+        that connection_pod_to_internet(pods[s], a, *probes[p]) == action
+        ("egress") or connection_internet_to_pod(a, pods[s], *probes[p]) ==
+        action ("ingress") for every address a of the range
+        (ConnectionPodToInternet :303-346, ConnectionInternetToPod :349-390),
+        probes being (proto, sport, dport) triples and dir the name given in
+        ``dirs``.  One engine call (Engine.reach_external) over the pods that
+        reach testConnection; a pod the reference fails before it
+        (unregistered, on another node, without an interface, or with an
+        empty node output interface name) has the one range (0, 0xFFFFFFFF,
+        CONN_FAILURE)."""
+        dirs = [dirs] if isinstance(dirs, str) else list(dirs)
+        for d in dirs:
+            if d not in ("egress", "ingress"):
+                raise ClsError("connection external: dirs names 'egress' and / or 'ingress'")
+        out = {(d, p, s): [(0, 0xFFFFFFFF, CONN_FAILURE)]
+               for d in dirs for p in range(len(probes)) for s in range(len(pods))}
+        ext = self._node_output_if()
+        eps = []
+        for i, pod in enumerate(pods):
+            cfg = self.pods.get(pod)
+            if cfg is None or cfg[1] or ext == "":
+                continue
+            ifn, ok = self.contiv.get_if_name(pod.namespace, pod.name)
+            if ok:
+                eps.append((i, self.engine.if_id(ifn), cfg[0]))
+        if not eps or not probes or not dirs:
+            return out
+        pr = np.array(probes, np.int64).reshape(-1, 3)
+        order = [d for d in ("egress", "ingress") if d in dirs]
+        r = self.engine.reach_external([e[1] for e in eps], self._matrix_addrs(eps), pr[:, 0], pr[:, 1], pr[:, 2],
+                                       self.engine.if_id(ext), dirs=order)
+        for e in eps:
+            for d in dirs:
+                for p in range(len(probes)):
+                    out[(d, p, e[0])] = []
+        for c in r["ranges"]:
+            out[(("egress", "ingress")[c["dir"]], int(c["probe"]), eps[c["src"]][0])].append(
+                (int(c["addr_lo"]), int(c["addr_hi"]), int(c["action"])))
+        return out
 
     def connection_matrix_diff(self, pods, probes, base, count: bool = False):
         """connection_matrix against a baseline: (matrix, changes), matrix
