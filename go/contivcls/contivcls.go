@@ -1522,6 +1522,68 @@ func (en *Engine) ConnCounters(aclName string, reset bool) ([]uint64, error) {
 	return out, nil
 }
 
+// Witness is the least packet, in (Src, Dst, Protocol, DstPort) order, that
+// terminates at a rule: addresses in host order, Protocol 0 TCP, 1 UDP, 2 ICMP
+// and 3 standing for every other value.
+type Witness struct {
+	Src, Dst uint32
+	Protocol uint8
+	DstPort  uint16
+}
+
+// Coverage is TableCover's answer for one installed ACL: Dead, the indices of
+// the rules no IPv4 packet can terminate at; Witnesses, rule index -> a packet
+// that terminates there; DefaultReachable, whether some packet falls through
+// to the default DENY; Cells, the cells of the class product the engine swept.
+type Coverage struct {
+	Dead             []int
+	Witnesses        map[int]Witness
+	DefaultReachable bool
+	Cells            uint64
+}
+
+// TableCover answers "which rules of this ACL can never be the matched rule,
+// and which packet matches each of the others?" in one engine call
+// (cls_table_cover): the engine sweeps every cell of source class x
+// destination class x (protocol, port class) of the ACL's compiled table on
+// the device.  The sweep covers the IPv4 packet space: a rule that only native
+// IPv6 packets can reach is reported dead.  The reference has no counterpart;
+// the closest is the matched rule evalACL logs at Debug.
+func (en *Engine) TableCover(aclName string) (*Coverage, error) {
+	en.Lock()
+	defer en.Unlock()
+	var strs cstrs
+	defer strs.free()
+	var id C.uint32_t
+	if rc := C.cls_acl_table(en.e, strs.add(aclName), &id); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	var info C.cls_table_info
+	if rc := C.cls_table_get_info(en.e, id, &info); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	r := int(info.n_rules)
+	live := make([]uint8, r+1)
+	rec := make([]uint32, 4*(r+1)) // 16-byte records: src, dst, dport | proto << 16 | live << 24, 0
+	var cells C.uint64_t
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds the struct on the C stack
+	if rc := C.clsg_table_cover_v4(en.e, id, (*C.uint8_t)(&live[0]), unsafe.Pointer(&rec[0]), nil, nil, &cells, nil,
+		0); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	out := &Coverage{Witnesses: make(map[int]Witness), DefaultReachable: live[r] != 0, Cells: uint64(cells)}
+	for k := 0; k < r; k++ {
+		if live[k] == 0 {
+			out.Dead = append(out.Dead, k)
+			continue
+		}
+		out.Witnesses[k] = Witness{Src: rec[4*k], Dst: rec[4*k+1], Protocol: uint8(rec[4*k+2] >> 16),
+			DstPort: uint16(rec[4*k+2])}
+	}
+	return out, nil
+}
+
 // ---- HBM-resident batches (ABI 4) -------------------------------------------
 // A Batch is engine-owned memory: packets stay in HBM between calls and no
 // Go pointer is ever kept by the library (cgo rule).  With mirror the batch

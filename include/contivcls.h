@@ -57,7 +57,10 @@ extern "C" {
  *    cls_reach_classes_host and the classes_key_bits option;
  *    cls_reach_external (per-pod remote address ranges over all of IPv4, to
  *    and from the node's output interface: cls_addr_range,
- *    cls_reach_ext_out, CLS_EXT_*) and cls_addr_classes. */
+ *    cls_reach_ext_out, CLS_EXT_*) and cls_addr_classes; cls_table_cover
+ *    (the rules of one table no packet terminates at and a witness packet
+ *    for each of the others: cls_cover_witness, cls_cover_out),
+ *    cls_cover_classes and the cover_tile option. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -208,7 +211,8 @@ int cls_abi_version(void);
  * pair_other_late, pair_o4, pair_map_lds, pair_class, conn_no_lds,
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
- * up to a multiple of 1024 --, hops_rows, classes_key_bits, debug_modes, debug_conn, debug_floor) for
+ * up to a multiple of 1024 --, cover_tile -- cls_table_cover's cells per tile,
+ * 1024 .. 2^30, rounded up likewise --, hops_rows, classes_key_bits, debug_modes, debug_conn, debug_floor) for
  * later calls; every one keeps verdicts and counters exact.  The library never reads the environment:
  * an engine runs its defaults unless told otherwise here.  CLS_E_INVAL for
  * an unknown key or a malformed value. */
@@ -785,6 +789,90 @@ int cls_reach_external(cls_engine* e, const cls_reach_spec* spec, uint32_t ext_i
  * string whose masked address is IPv4-mapped).  *n = K; with cap < K only *n
  * is set.  cls_reach_external uses the sorted union over the bound ACLs. */
 int cls_addr_classes(const cls_rule* rules, uint32_t n_rules, uint32_t* lo_out, uint32_t cap, uint32_t* n);
+
+/* ---- rule coverage sweep: dead rules and a witness packet per rule ---------
+ * "Which rules of this table can never be the matched rule, for any packet?
+ * For the others, show me a packet that matches each one."  The space is every
+ * IPv4 packet (src, dst, proto, dport): src and dst 0 .. 2^32 - 1, proto a
+ * uint8, dport 0 .. 65535; with af CLS_AF_V16 the same packets go to the
+ * 16-byte classifier as ::ffff:src / ::ffff:dst.  Native IPv6 packets are out
+ * of scope: a rule that only IPv6 packets can reach is reported dead by this
+ * IPv4 sweep.
+ * evalACL (aclengine_mock.go:473-668) sees a packet in four ways only: the
+ * source address in Contains tests of source networks, the destination address
+ * in Contains tests of destination networks, the protocol through one switch,
+ * the destination port in comparisons with the u16 range ends of that
+ * protocol's section.  So the terminating rule is constant on every cell of
+ *   Ks source classes: the elementary intervals whose starts are {0}, lo and
+ *      hi + 1 <= 2^32 - 1 of every SOURCE network of effective family 4
+ *      (cls_addr_classes' rules, per side: cls_cover_classes side 0);
+ *   Kd destination classes: the same of the DESTINATION networks (side 1);
+ *   T = Kt + Ku + 2 columns, in this order: the table's TCP port classes
+ *      ascending (cls_port_classes), its UDP port classes, one ICMP column
+ *      (port 0), one column for every other protocol value (representative:
+ *      protocol 3, port 0).
+ * Cell c = (s Kd + d) T + j; its representative is the lowest packet of each
+ * class, so ascending c is ascending (src, dst, proto, dport) of the
+ * representatives.  The engine evaluates the cells in tiles of cover_tile --
+ * cells expanded on the device, the matched-rule trace of cls_classify_rules
+ * unchanged, no counters touched -- and folds them there.
+ * "Terminates at k" is the counters' definition, whatever the action: a
+ * FAILURE at a rule counts for that rule; index R is the default DENY.
+ * Outputs (cls_cover_out), each optional:
+ *   live_out    [R+1] u8   1 iff some packet of the space terminates at rule k
+ *   witness_out [R+1]      the least such packet in (src, dst, proto, dport)
+ *                          order, protocol 3 standing for every value above
+ *                          2; all zero for a dead rule.  Canonical: it depends
+ *                          on the rule list's semantics alone, not on the
+ *                          classes, cover_tile, the evaluator or the
+ *                          scheduling (the least hitting packet is the low
+ *                          corner of the lowest hitting cell)
+ *   cells_out   [R+1] u64  the cells terminating at the rule: defined relative
+ *                          to the classes above, a deterministic function of
+ *                          the rule list; sums to Ks Kd T (every cell folded
+ *                          exactly once)
+ *   n_dead      1 word     rules k < R with live == 0
+ *   n_cells     HOST word, also with CLS_F_DEVICE: Ks Kd T
+ *   dims        HOST [4], also with CLS_F_DEVICE: Ks, Kd, Kt, Ku
+ * At least one of live_out, witness_out, cells_out, n_dead must be given.
+ * Flags: CLS_F_DEVICE -- those four are device memory (witness_out 16-byte,
+ * cells_out 8-byte, n_dead 4-byte aligned) and the call only enqueues on
+ * `stream`; without it they are host arrays filled through engine-owned
+ * buffers.  CLS_F_FORCE_LINEAR -- the linear kernel evaluates; it is the IPv4
+ * one in either layout (the sweep's 16-byte packets are IPv4-mapped, and the
+ * 16-byte layout's linear form writes no rule).  CLS_E_INVAL, before any
+ * device work and with every output untouched: af other than CLS_AF_V4 /
+ * CLS_AF_V16, a CLS_AF_V16 sweep of a table without a 16-byte classifier (as
+ * cls_classify_rules), `out` NULL or none of the four outputs, a misaligned
+ * device pointer, any other flag, Ks Kd T > 2^40 (the three factors in
+ * cls_last_error).  CLS_E_NOTFOUND: an unknown table.  The call takes the
+ * engine's lock and the table as classify calls do and restores the caller's
+ * device; on a multi-device engine it runs on the first device. */
+typedef struct cls_cover_witness {   /* 16 bytes */
+    uint32_t src, dst;               /* host-order IPv4 */
+    uint16_t dport;
+    uint8_t proto;                   /* 0, 1, 2, or 3 standing for every value > 2 */
+    uint8_t live;                    /* 1: some packet terminates at this rule */
+    uint32_t zero;
+} cls_cover_witness;
+
+typedef struct cls_cover_out {
+    uint8_t* live_out;               /* [R+1]  index R: the default DENY */
+    cls_cover_witness* witness_out;  /* [R+1] */
+    uint64_t* cells_out;             /* [R+1]  cells terminating at the rule; sums to Ks Kd T */
+    uint32_t* n_dead;                /* 1 word: rules k < R with live == 0 */
+    uint64_t* n_cells;               /* HOST word, also with CLS_F_DEVICE: Ks Kd T */
+    uint32_t* dims;                  /* HOST [4], optional: Ks, Kd, Kt, Ku */
+} cls_cover_out;
+
+int cls_table_cover(cls_engine* e, uint32_t table_id, uint32_t af, const cls_cover_out* out, uint32_t flags,
+                    void* stream);
+/* The class starts of one side of a rule list (no device needed; side 0 =
+ * source networks, 1 = destination networks): ascending, lo_out[0] == 0, as
+ * cls_addr_classes over that side alone.  *n = K; with cap < K only *n is
+ * set.  CLS_E_INVAL: side above 1. */
+int cls_cover_classes(const cls_rule* rules, uint32_t n_rules, uint32_t side, uint32_t* lo_out, uint32_t cap,
+                      uint32_t* n);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

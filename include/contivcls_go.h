@@ -497,6 +497,41 @@ static inline int clsg_reach_external_v16(cls_engine* e, const uint32_t* if_id, 
     return cls_reach_external(e, &r, ext_if, dirs, &o, flags, NULL);
 }
 
+/* cls_table_cover of one table over the IPv4 packet space, IPv4 layout: which
+ * rules no packet terminates at and a witness packet for each of the others.
+ * Host arrays over the table's r rules and the default DENY at index r; live
+ * (r + 1 u8), witness (r + 1 records of 16 bytes: src and dst as u32, dport as
+ * u16, proto and live as u8, a zero u32), cells (r + 1 u64) and n_dead (1) may
+ * each be NULL, but not all; n_cells (1) and dims (4: Ks, Kd, Kt, Ku) may be
+ * NULL. */
+static inline int clsg_table_cover_v4(cls_engine* e, uint32_t table_id, uint8_t* live, void* witness, uint64_t* cells,
+                                      uint32_t* n_dead, uint64_t* n_cells, uint32_t* dims, uint32_t flags) {
+    cls_cover_out o;
+    memset(&o, 0, sizeof o);
+    o.live_out = live;
+    o.witness_out = (cls_cover_witness*)witness;
+    o.cells_out = cells;
+    o.n_dead = n_dead;
+    o.n_cells = n_cells;
+    o.dims = dims;
+    return cls_table_cover(e, table_id, CLS_AF_V4, &o, flags, NULL);
+}
+
+/* The same sweep through the 16-byte classifier: the packets are the
+ * IPv4-mapped ::ffff:src / ::ffff:dst. */
+static inline int clsg_table_cover_v16(cls_engine* e, uint32_t table_id, uint8_t* live, void* witness, uint64_t* cells,
+                                       uint32_t* n_dead, uint64_t* n_cells, uint32_t* dims, uint32_t flags) {
+    cls_cover_out o;
+    memset(&o, 0, sizeof o);
+    o.live_out = live;
+    o.witness_out = (cls_cover_witness*)witness;
+    o.cells_out = cells;
+    o.n_dead = n_dead;
+    o.n_cells = n_cells;
+    o.dims = dims;
+    return cls_table_cover(e, table_id, CLS_AF_V16, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -59,7 +59,8 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_classify_batch", "cls_batch_counters", "cls_batch_connect", "cls_batch_wait", "cls_comm_unique_id",
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
            "cls_port_classes", "cls_reach_hops", "cls_reach_classes",
-           "cls_reach_classes_host", "cls_reach_external", "cls_addr_classes"]
+           "cls_reach_classes_host", "cls_reach_external", "cls_addr_classes", "cls_table_cover",
+           "cls_cover_classes"]
 
 
 class ClsRule(C.Structure):
@@ -151,6 +152,16 @@ EXT_EGRESS, EXT_INGRESS = 1, 2
 # cls_addr_range as a numpy structured dtype (16 bytes)
 ADDR_RANGE = np.dtype([("src", "<u4"), ("probe", "<u2"), ("dir", "u1"), ("action", "u1"), ("addr_lo", "<u4"),
                        ("addr_hi", "<u4")])
+
+class CoverOut(C.Structure):
+    """cls_cover_out: the outputs of cls_table_cover, each optional."""
+    _fields_ = [("live_out", C.c_void_p), ("witness_out", C.c_void_p), ("cells_out", C.c_void_p),
+                ("n_dead", C.c_void_p), ("n_cells", C.c_void_p), ("dims", C.c_void_p)]
+
+
+# cls_cover_witness as a numpy structured dtype (16 bytes)
+COVER_WITNESS = np.dtype([("src", "<u4"), ("dst", "<u4"), ("dport", "<u2"), ("proto", "u1"), ("live", "u1"),
+                          ("zero", "<u4")])
 
 # cls_reach_classes: quot[p][A][A] of a one-member class
 CLASS_NONE = 255
@@ -298,6 +309,8 @@ def bind(path: str, strict: bool = True):
         "cls_reach_classes_host": (C.c_int, [vp, u32, u32, u32, C.POINTER(ReachClassesOut)]),
         "cls_reach_external": (C.c_int, [vp, C.POINTER(ReachSpec), u32, u32, C.POINTER(ReachExtOut), u32, vp]),
         "cls_addr_classes": (C.c_int, [vp, u32, vp, u32, C.POINTER(u32)]),
+        "cls_table_cover": (C.c_int, [vp, u32, u32, C.POINTER(CoverOut), u32, vp]),
+        "cls_cover_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <iterator>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -365,7 +366,11 @@ static int table_compile(cls_engine* e, const char* name, const cls_rule* rules,
     if (rc != CLS_OK) return fail(e, rc, "%s", why.c_str());
     t->conn16 = conn_rules16(s16);
     for (uint32_t p = 0; p < 2; ++p) t->port_lo[p] = port_class_starts(rules, n, p);
-    t->addr_lo = addr_class_starts(rules, n);
+    // each network string is parsed once: the two sides' starts, and their union (addr_class_starts(rules, n))
+    for (uint32_t sd = 0; sd < 2; ++sd) t->cover_lo[sd] = cover_side_starts(rules, n, sd);
+    t->addr_lo.clear();
+    std::set_union(t->cover_lo[0].begin(), t->cover_lo[0].end(), t->cover_lo[1].begin(), t->cover_lo[1].end(),
+                   std::back_inserter(t->addr_lo));
     std::string why16;
     q.ok = build_cls16(s16, n, q.img, why16) && build_other4(q.img.sem, n, q.oimg, why16);
     q.why = why16;
@@ -406,6 +411,7 @@ std::shared_ptr<Table> table_clone_host(const Table& s) {
     t->conn16 = s.conn16;
     for (int p = 0; p < 2; ++p) t->port_lo[p] = s.port_lo[p];
     t->addr_lo = s.addr_lo;
+    for (int sd = 0; sd < 2; ++sd) t->cover_lo[sd] = s.cover_lo[sd];
     t->conn_bm = s.conn_bm;
     t->conn_bm_built = s.conn_bm_built;
     t->conn_epoch = s.conn_epoch;
@@ -751,12 +757,15 @@ static int classify16_locked(cls_engine* e, std::shared_ptr<Table> t, const cls_
     return finish_counts(e, *t, t->c16, sc, co, n, verdict_out, d_verdict, counters_out, flags, s, remapped);
 }
 
+}  // extern "C"
+
 // Each packet's ACLAction and terminating rule (the debug trace of
 // evalACL's matched rule, aclengine_mock.go:651-654): the classify kernels'
 // slot mode, then slot -> rule; tables without a classifier image run the
-// linear kernel.  No counters are touched.
-static int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n,
-                                 uint8_t* verdict_out, uint32_t* rule_out, uint32_t flags, void* stream) {
+// linear kernel (cls_table_cover's CLS_F_FORCE_LINEAR, `linear`: an IPv4 batch
+// of any table).  No counters are touched.
+int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n, uint8_t* verdict_out,
+                          uint32_t* rule_out, uint32_t flags, void* stream, bool linear) {
     auto it = e->tables.find(table_id);
     if (it == e->tables.end()) return fail(e, CLS_E_NOTFOUND, "no table %u", table_id);
     const std::shared_ptr<Table> t = it->second;
@@ -824,7 +833,7 @@ static int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt
             const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src) + off;
             const uint32_t* d4 = reinterpret_cast<const uint32_t*>(dst) + off;
             const Pkts4 pc{s4, d4, dp + off, pr + off, m};
-            if (t->has_cls) {
+            if (t->has_cls && !linear) {
                 cfg.other = cls4_dev(t->oimg, t->d_oimg, DevBuf(), 0, t->n_rules);
                 cfg.grid = cls_grid(e, true, t->lds_resident, t->img.lds_bytes, m);
                 HIPC(e, launch_classify4_slots(table_dev(*t), framed(t->img, pc), ro, t->lds_resident, cfg));
@@ -843,6 +852,8 @@ static int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt
     }
     return CLS_OK;
 }
+
+extern "C" {
 
 int cls_classify_rules(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n, uint8_t* verdict_out,
                        uint32_t* rule_out, uint32_t flags, void* stream) {

@@ -154,6 +154,9 @@ struct Table {
     // cls_reach_external: the table's IPv4 address class starts
     // (addr_class_starts: sorted, unique, the first is 0)
     std::vector<uint32_t> addr_lo;
+    // cls_table_cover: the class starts of the source (0) and the destination
+    // (1) networks alone (cover_side_starts: sorted, unique, the first is 0)
+    std::vector<uint32_t> cover_lo[2];
     // the bitmap form of conn4 (conn_bitmap4), built on the first connection
     // batch that wants it; empty when its tables exceed kConnBmMaxWords
     std::vector<uint32_t> conn_bm;
@@ -265,6 +268,12 @@ struct cls_engine {
     // pass's flag, the candidate classes, the verify table and a host call's
     // class_out (a host matrix's tiles use r_base)
     DevBuf r_csums, r_cdiag, r_cmask, r_ccls, r_ctab;
+    // cls_table_cover (cover.cpp), under the same rule: the call's class tables
+    // (cover_up their host copy), a tile's packet arrays and terminating rules,
+    // the per-rule least cell and cell count (u64 each), the outputs a host
+    // call downloads (witnesses, live bytes, n_dead)
+    DevBuf v_tab, v_src, v_dst, v_dport, v_proto, v_rule, v_min, v_cnt, v_wit, v_live, v_dead;
+    std::vector<uint8_t> cover_up;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits
@@ -361,6 +370,13 @@ std::vector<uint16_t> port_class_starts(const cls_rule* rules, uint32_t n, uint3
 // -- 0, and lo and hi + 1 <= 2^32 - 1 of every source or destination network
 // that parse_cidr reduces to family 4; sorted and unique
 std::vector<uint32_t> addr_class_starts(const cls_rule* rules, uint32_t n);
+// cover.cpp (cls_cover_classes): the same over the source (side 0) or the
+// destination (side 1) networks alone
+std::vector<uint32_t> cover_side_starts(const cls_rule* rules, uint32_t n, uint32_t side);
+// engine.cpp (the caller holds e->mu): what cls_classify_rules runs; linear:
+// an IPv4 batch on the linear kernel also where the table has an image
+int classify_rules_locked(cls_engine* e, uint32_t table_id, const cls_pkt_soa* pk, uint64_t n, uint8_t* verdict_out,
+                          uint32_t* rule_out, uint32_t flags, void* stream, bool linear = false);
 
 // ---- engine.cpp / connect.cpp internals used by fleet.cpp (the caller holds e->mu)
 int engine_open(int device, cls_engine** out);

@@ -537,6 +537,38 @@ hipError_t launch_reach_ext_count(const ReachExtTile& t, const uint8_t* verdict,
 hipError_t launch_reach_ext_emit(const ReachExtTile& t, const uint8_t* verdict, const unsigned long long* chunk_base,
                                  uint4* ranges, unsigned long long cap, int n_cu, hipStream_t s);
 
+// ---- the rule coverage sweep (k_cover.hip; contivcls.h cls_table_cover) ----
+// One tile of the sweep: the n <= 2^30 cells from global cell c0 on, cell c =
+// (s Kd + d) T + j (source class s, destination class d, column j), up to 2^40
+// of them in all.  slo / dlo: the class starts (ascending, [0] == 0); col: the
+// T columns as dport | proto << 16.
+struct CoverTile {
+    unsigned long long c0;
+    uint32_t n;
+    uint32_t Kd, T;
+    const uint32_t *slo, *dlo, *col;
+};
+// The tile's cells as a device classify batch's arrays, in reach_expand's
+// store shape (four cells per lane, the last group padded by repetition: the
+// arrays hold (n + 3) / 4 whole groups): each cell's lowest packet -- the
+// class starts (16-byte layout: ::ffff:a), the column's protocol and port.
+hipError_t launch_cover_expand(const CoverTile& t, bool k16, void* src, void* dst, uint16_t* dport, uint8_t* proto,
+                               int n_cu, hipStream_t s);
+// rule: the tile's n terminating rules (16-B aligned), each below n_out = R + 1.
+// minc[r] = min(minc[r], the least global cell c0 + i with rule[i] == r);
+// cnt[r] += the cells with rule r.  Runs of equal rules reduce in the wave,
+// then across the workgroup's waves, before any global atomic.
+// Up to 15,360 rules the counts pass through per-workgroup LDS bins
+// (cover_fold_bins), above that the run heads add to cnt directly.
+hipError_t launch_cover_fold(unsigned long long c0, uint32_t n, const uint32_t* rule, uint32_t n_out,
+                             unsigned long long* minc, unsigned long long* cnt, int n_cu, hipStream_t s);
+// Once per call, over the n_out rules (t: the class tables; c0 and n unused):
+// minc[k] == ~0: dead -- live 0, an all-zero witness, and one more in *n_dead
+// (cleared before) when k < R; else live 1 and the witness {src, dst, dport |
+// proto << 16 | 1 << 24, 0} of the cell.  live_out, witness, n_dead may be null.
+hipError_t launch_cover_finish(const CoverTile& t, const unsigned long long* minc, uint32_t n_out, uint8_t* live_out,
+                               uint4* witness, uint32_t* n_dead, hipStream_t s);
+
 // ---- the hop closure (k_reach_hops.hip; contivcls.h cls_reach_hops) --------
 // fold: the tile's CLS_CONN_ALLOW cells off the diagonal as bits of the
 // adjacency bitmap adj[N][W], W = (N + 63) / 64 -- bit (d & 63) of word

@@ -97,6 +97,15 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
         o.reach_tile = reset ? d.reach_tile : uint32_t((x + 1023) & ~1023ll);
         return true;
     }
+    if (k == "cover_tile") {
+        // a tile is one classify launch (at most 2^30 packets)
+        if (!reset && (x < 1024 || x > (1ll << 30))) {
+            why = "option cover_tile: 1024 .. 2^30 cells";
+            return false;
+        }
+        o.cover_tile = reset ? d.cover_tile : uint32_t((x + 1023) & ~1023ll);
+        return true;
+    }
     if (k == "hops_rows") {
         if (!reset && x != 0 && x != 4 && x != 8 && x != 16) {
             why = "option hops_rows: 0 (the default), 4, 8 or 16 source rows per workgroup";

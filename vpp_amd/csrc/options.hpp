@@ -59,6 +59,8 @@ struct Opts {
     // ---- reachability matrix (reach.cpp) ----------------------------------
     uint32_t reach_tile = 16u << 20; // connections per tile (>= 256, rounded up to a multiple of 1024; 16 Mi
                                      // measured best of 1 / 4 / 16 Mi, profiles/reach_ab_af{4,16}.txt)
+    uint32_t cover_tile = 16u << 20; // cls_table_cover: cells per tile (1024 .. 2^30, rounded up to a multiple of 1024; 16 Mi
+                                     // measured best of 1 / 4 / 16 Mi on config 3, profiles/cover_ab_af{4,16}.txt)
     uint32_t hops_rows = 0;     // cls_reach_hops: source rows per workgroup of the search, 4, 8 or 16 (0: 4, the
                                 // best of the three measured, profiles/reach_hops_ab_af{4,16}.txt; halved while
                                 // the rows do not fit 64 KiB of LDS)

@@ -800,6 +800,79 @@ class Engine:
             raise ClsError("cls_addr_classes: rc=%d" % rc)
         return lo
 
+    @staticmethod
+    def cover_classes(rules, side: int) -> np.ndarray:
+        """The IPv4 address class starts of one side of a rule list
+        (cls_cover_classes; no device): side 0 the source networks, 1 the
+        destination networks; ascending u32, the first 0."""
+        cr = rules if isinstance(rules, _abi.CRules) else _abi.CRules(rules)
+        n = C.c_uint32(0)
+        rc = _abi.lib().cls_cover_classes(cr.ptr(), cr.n, int(side), None, 0, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_cover_classes: rc=%d" % rc)
+        lo = np.zeros(n.value, np.uint32)
+        rc = _abi.lib().cls_cover_classes(cr.ptr(), cr.n, int(side), _ptr(lo), n.value, C.byref(n))
+        if rc != 0:
+            raise ClsError("cls_cover_classes: rc=%d" % rc)
+        return lo
+
+    def table_cover(self, table, af: int = 4, mode: str = "auto", out=None, stream=None):
+        """The rule coverage sweep (cls_table_cover) of one table over the whole
+        IPv4 packet space (``af`` 16: the same packets as ::ffff:a in the
+        16-byte layout): which rules no packet terminates at, and the least
+        packet in (src, dst, proto, dport) order that terminates at each of
+        the others.  Returns a dict: live uint8 [R+1] (index R: the default
+        DENY), witness [R+1] (_abi.COVER_WITNESS: src, dst, dport, proto --
+        3 standing for every protocol above 2 --, live; zeros for a dead
+        rule), cells uint64 [R+1] (cells of the class product terminating at
+        the rule; sums to n_cells), n_dead (rules below R that are dead),
+        n_cells (Ks Kd T) and dims (Ks, Kd, Kt, Ku).  mode "linear": the
+        linear kernel evaluates.
+        out None: the host form -- numpy results, n_dead an int.
+        out a sequence (live, witness, cells, n_dead) of contiguous torch GPU
+        tensors (None allocates one): the device form -- live uint8 [R+1],
+        witness int32 [R+1, 4] rows of (src, dst, dport | proto << 16 | live
+        << 24, 0), cells int64 [R+1], n_dead int32 [1]; the call only enqueues
+        on ``stream`` (default: the engine's).  n_cells and dims are host
+        values either way."""
+        flags = {"auto": 0, "linear": _abi.F_FORCE_LINEAR}[mode]
+        tid = table.id if isinstance(table, Table) else int(table)
+        r = (table.n_rules if isinstance(table, Table) else self._table_rules(tid)) + 1
+        n_cells, dims = np.zeros(1, np.uint64), np.zeros(4, np.uint32)
+        fn = _abi.lib().cls_table_cover
+        names = ("live", "witness", "cells", "n_dead")
+        if out is None:
+            live, wit = np.zeros(r, np.uint8), np.zeros(r, _abi.COVER_WITNESS)
+            cells, dead = np.zeros(r, np.uint64), np.zeros(1, np.uint32)
+            o = _abi.CoverOut(_ptr(live), _ptr(wit), _ptr(cells), _ptr(dead), _ptr(n_cells), _ptr(dims))
+            self._check(fn(self.h, tid, int(af), C.byref(o), flags, None))
+            return dict(zip(names, (live, wit, cells, int(dead[0]))), n_cells=int(n_cells[0]),
+                        dims=tuple(int(x) for x in dims))
+        import torch
+        res = list(out)
+        if len(res) != 4:
+            raise ClsError("table cover: out is (live, witness, cells, n_dead)")
+        shapes = ((r,), (r, 4), (r,), (1,))
+        kinds = ((torch.uint8, 1), (torch.int32, 4), (torch.int64, 8), (torch.int32, 4))
+        for i, (sh, (dt, sz)) in enumerate(zip(shapes, kinds)):
+            if res[i] is None:
+                res[i] = torch.empty(sh, dtype=dt, device="cuda")
+            elif not (_is_torch(res[i]) and res[i].is_cuda and res[i].is_contiguous() and
+                      res[i].element_size() == sz and tuple(res[i].shape) == sh):
+                raise ClsError("table cover: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                               "elements" % (i, sh, sz))
+        s = None
+        if stream is not None:
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.CoverOut(_ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), _ptr(n_cells), _ptr(dims))
+        self._check(fn(self.h, tid, int(af), C.byref(o), flags | _abi.F_DEVICE, s))
+        return dict(zip(names, res), n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
+
+    def _table_rules(self, tid: int) -> int:
+        inf = _abi.TableInfo()
+        self._check(_abi.lib().cls_table_get_info(self.h, tid, C.byref(inf)))
+        return int(inf.n_rules)
+
     def reach_external(self, if_ids, addrs, protos, sports, dports, ext_if: int, dirs=("egress", "ingress"),
                        cap=None, mode: str = "auto", out=None, stream=None):
         """The external sweep (cls_reach_external): which remote IPv4
@@ -1555,6 +1628,32 @@ class ACLEngine:
             out[(("egress", "ingress")[c["dir"]], int(c["probe"]), eps[c["src"]][0])].append(
                 (int(c["addr_lo"]), int(c["addr_hi"]), int(c["action"])))
         return out
+
+    def acl_coverage(self, acl_name: str, af: int = 4):
+        """Which rules of an installed ACL can never be the matched rule, and a
+        packet for each of the others (Engine.table_cover over the ACL's
+        compiled table; the reference has no such call -- the closest is the
+        matched rule evalACL logs at Debug).  Returns a dict: ``dead``, the
+        indices of the rules no packet terminates at; ``witness``, rule index
+        -> (src string, dst string, protocol, dport), the least packet in
+        (src, dst, protocol, dport) order that terminates at the rule,
+        protocol 3 standing for every value above 2; ``default_reachable``,
+        whether some packet falls through to the default DENY.  The sweep
+        covers the IPv4 packet space only (``af`` 16: the same packets in the
+        16-byte layout): a rule that only native IPv6 packets can reach is
+        reported dead.  Raises ClsError for an unknown name."""
+        tid = self.engine.acl_table(acl_name)
+        if acl_name not in self.by_name or tid < 0:
+            raise ClsError("acl coverage: no ACL %r" % (acl_name,))
+        r = self.engine.table_cover(tid, af=af)
+        n = len(r["live"]) - 1
+
+        def ip(a):
+            return "%d.%d.%d.%d" % (a >> 24, a >> 16 & 255, a >> 8 & 255, a & 255)
+        wit = {k: (ip(int(w["src"])), ip(int(w["dst"])), int(w["proto"]), int(w["dport"]))
+               for k, w in enumerate(r["witness"][:n]) if w["live"]}
+        return {"dead": [k for k in range(n) if not r["live"][k]], "witness": wit,
+                "default_reachable": bool(r["live"][n])}
 
     def connection_matrix_diff(self, pods, probes, base, count: bool = False):
         """connection_matrix against a baseline: (matrix, changes), matrix
