@@ -71,7 +71,9 @@ def test_reference_scenarios_on_gpu(eng, test):
 @pytest.mark.parametrize("n_rules,weird", [(5, 0.0), (60, 0.0), (60, 0.25), (400, 0.05)])
 def test_random_acls_both_kernels(eng, seed, n_rules, weird):
     rules, pool = random_acl(seed * 7919 + n_rules, n_rules, weird)
-    tr = random_traffic(seed, 20011, pool)           # odd length: vector body + scalar tail
+    # odd length below one full grid step: classify4_cls's leftover groups of
+    # four and its per-packet tail (the full-step loop: test_gpu_classify_steps.py)
+    tr = random_traffic(seed, 20011, pool)
     want = _oracle(rules, tr)
     _assert_same(_gpu(eng, rules, tr), want)
     _assert_same(_gpu(eng, rules, tr, force_linear=True), want)

@@ -52,7 +52,9 @@ def _img16(rules):
 @pytest.mark.parametrize("kind", sorted(VARIANTS))
 def test_rules_v4_variants(eng, libopt, kind, seed):
     """Every source lookup x list mode of the IPv4 classifier, LDS-resident,
-    host arrays (the vector body of dispatch_slots4 and its tail)."""
+    host arrays (the vector kernel of dispatch_slots4: at these sizes its
+    leftover groups of four and its tail; its full-step loop is reached in
+    test_gpu_classify_steps.py)."""
     for k, v in variant_options(kind, 4).items():
         libopt.set(k, v, eng)
     rules, pool = variant_acl(kind, seed)

@@ -35,7 +35,7 @@ def _oracle16(rules, tr, fast=False):
 @pytest.mark.parametrize("n_rules,weird", [(5, 0.0), (60, 0.0), (60, 0.25), (300, 0.05)])
 def test_v16_random_acls_both_kernels(eng, seed, n_rules, weird):
     rules, pool = random_acl16(seed * 7919 + n_rules, n_rules, weird)
-    tr = random_traffic16(seed, 6007, pool)          # odd length: vector body + scalar tail
+    tr = random_traffic16(seed, 6007, pool)          # 23 whole 256-packet wave-steps + a 119-packet tail
     want = _oracle16(rules, tr)
     _assert_same(_gpu(eng, rules, tr), want)
     _assert_same(_gpu(eng, rules, tr, force_linear=True), want)
