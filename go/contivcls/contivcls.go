@@ -1584,6 +1584,102 @@ func (en *Engine) TableCover(aclName string) (*Coverage, error) {
 	return out, nil
 }
 
+// DiffRecord is one run of packets whose ACLAction differs between two ACLs:
+// source and destination address ranges (host order, inclusive), Protocol 0
+// TCP, 1 UDP, 2 ICMP and 3 standing for every other value, the destination
+// port range (0 .. 65535 where the protocol has no port), the action under
+// the first ACL (Was) and under the second (Now), and the rule each one's
+// evaluation terminated at (the rule count: the default DENY).
+type DiffRecord struct {
+	SrcLo, SrcHi, DstLo, DstHi uint32
+	PortLo, PortHi             uint16
+	Protocol, Was, Now         uint8
+	RuleA, RuleB               int
+}
+
+// Diff is TableDiff's answer for two installed ACLs: Equal, whether every IPv4
+// packet gets the same ACLAction under both; Pairs[was][now], the cells of the
+// joint class product per pair of actions; First, the least differing packet
+// (nil if none); Records, the differing packets in ascending order; RulesA and
+// RulesB, rule index -> the least differing packet that terminates there.
+type Diff struct {
+	Equal   bool
+	Cells   uint64
+	Pairs   [4][4]uint64
+	First   *Witness
+	Records []DiffRecord
+	RulesA  map[int]Witness
+	RulesB  map[int]Witness
+}
+
+func diffWitnesses(rec []uint32, r int) map[int]Witness {
+	out := make(map[int]Witness)
+	for k := 0; k <= r; k++ {
+		if rec[4*k+2]>>24 == 0 {
+			continue
+		}
+		out[k] = Witness{Src: rec[4*k], Dst: rec[4*k+1], Protocol: uint8(rec[4*k+2] >> 16), DstPort: uint16(rec[4*k+2])}
+	}
+	return out
+}
+
+// TableDiff answers "is ACL b semantically the same as ACL a, and if not, for
+// exactly which packets does the verdict change, and which rules are
+// responsible?" (cls_table_diff): the engine evaluates every cell of the two
+// compiled tables' joint classes under both on the device and compares there.
+// Two calls: the first counts the records, the second takes them.  The diff
+// covers the IPv4 packet space.  The reference has no counterpart.
+func (en *Engine) TableDiff(aclA, aclB string) (*Diff, error) {
+	en.Lock()
+	defer en.Unlock()
+	var strs cstrs
+	defer strs.free()
+	var ids [2]C.uint32_t
+	var rules [2]int
+	for i, name := range []string{aclA, aclB} {
+		if rc := C.cls_acl_table(en.e, strs.add(name), &ids[i]); rc != C.CLS_OK {
+			return nil, en.lastErr()
+		}
+		var info C.cls_table_info
+		if rc := C.cls_table_get_info(en.e, ids[i], &info); rc != C.CLS_OK {
+			return nil, en.lastErr()
+		}
+		rules[i] = int(info.n_rules)
+	}
+	var nRec, nDiff, cells C.uint64_t
+	if rc := C.clsg_table_diff_v4(en.e, ids[0], ids[1], nil, nil, nil, nil, nil, nil, nil, nil, 0, &nRec, nil, nil,
+		0); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds the struct on the C stack
+	pairs := make([]uint64, 16)
+	first := make([]uint32, 4)
+	witA := make([]uint32, 4*(rules[0]+1)) // 16-byte records: src, dst, dport | proto << 16 | live << 24, 0
+	witB := make([]uint32, 4*(rules[1]+1))
+	rec := make([]uint32, 8*(int(nRec)+1)) // 32-byte records
+	if rc := C.clsg_table_diff_v4(en.e, ids[0], ids[1], &nDiff, (*C.uint64_t)(&pairs[0]), unsafe.Pointer(&first[0]),
+		nil, unsafe.Pointer(&witA[0]), nil, unsafe.Pointer(&witB[0]), unsafe.Pointer(&rec[0]), nRec, &nRec, &cells,
+		nil, 0); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	out := &Diff{Equal: nDiff == 0, Cells: uint64(cells), RulesA: diffWitnesses(witA, rules[0]),
+		RulesB: diffWitnesses(witB, rules[1])}
+	for i := 0; i < 16; i++ {
+		out.Pairs[i/4][i%4] = pairs[i]
+	}
+	if first[2]>>24 != 0 {
+		out.First = &Witness{Src: first[0], Dst: first[1], Protocol: uint8(first[2] >> 16), DstPort: uint16(first[2])}
+	}
+	for k := 0; k < int(nRec) && 8*k+7 < len(rec); k++ {
+		w := rec[8*k : 8*k+8]
+		out.Records = append(out.Records, DiffRecord{SrcLo: w[0], SrcHi: w[1], DstLo: w[2], DstHi: w[3],
+			PortLo: uint16(w[4]), PortHi: uint16(w[4] >> 16), Protocol: uint8(w[5]), Was: uint8(w[5] >> 8),
+			Now: uint8(w[5] >> 16), RuleA: int(w[6]), RuleB: int(w[7])})
+	}
+	return out, nil
+}
+
 // ---- HBM-resident batches (ABI 4) -------------------------------------------
 // A Batch is engine-owned memory: packets stay in HBM between calls and no
 // Go pointer is ever kept by the library (cgo rule).  With mirror the batch

@@ -60,7 +60,9 @@ extern "C" {
  *    cls_reach_ext_out, CLS_EXT_*) and cls_addr_classes; cls_table_cover
  *    (the rules of one table no packet terminates at and a witness packet
  *    for each of the others: cls_cover_witness, cls_cover_out),
- *    cls_cover_classes and the cover_tile option. */
+ *    cls_cover_classes and the cover_tile option; cls_table_diff (the packets
+ *    whose verdict differs between two tables, as records over the joint
+ *    classes, and the rules responsible: cls_tdiff_rec, cls_tdiff_out). */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -873,6 +875,88 @@ int cls_table_cover(cls_engine* e, uint32_t table_id, uint32_t af, const cls_cov
  * set.  CLS_E_INVAL: side above 1. */
 int cls_cover_classes(const cls_rule* rules, uint32_t n_rules, uint32_t side, uint32_t* lo_out, uint32_t cap,
                       uint32_t* n);
+
+/* ---- table diff: packets whose verdict differs between two rule lists -------
+ * "Is table b semantically the same as table a?  If not, for exactly which
+ * packets does the verdict change, and which rules are responsible?"  The
+ * space, the cells and their order are cls_table_cover's: every IPv4 packet
+ * (src, dst, proto, dport), with af CLS_AF_V16 the same packets as ::ffff:a in
+ * the 16-byte layout; native IPv6 packets are out of scope.  Both tables'
+ * verdicts are constant on every cell of the JOINT classes -- per side and per
+ * protocol the sorted union of the two tables' class starts, which equals
+ * cls_cover_classes / cls_port_classes over the two rule lists concatenated
+ * (a's rules, then b's) -- so Ks, Kd, Kt, Ku, T = Kt + Ku + 2, the cell index
+ * c = (s Kd + d) T + j and the columns are cover's over that list.  The engine
+ * evaluates the cells in tiles of whole rows (max(1, cover_tile / T) rows of T
+ * cells) under both tables with the matched-rule trace of cls_classify_rules,
+ * unchanged, and compares on the device.
+ * A cell differs iff the two ACLActions differ.  Equal verdicts through
+ * different rules are no difference: rule indices of different tables are not
+ * comparable.  table_a == table_b is allowed and yields none.
+ * Records (cls_tdiff_rec): one per maximal run of consecutive differing cells
+ * that lies within one (source class, destination class) row and one protocol
+ * and whose cells have equal (was, now, rule_a, rule_b); in ascending cell
+ * order.  src_hi, dst_hi and port_hi are the next class start minus one, or the
+ * top of the range.  The first min(rec_cap, total) records are written; *n_rec
+ * is the total either way.
+ * Outputs (cls_tdiff_out), each optional:
+ *   n_diff    1 u64        cells with was != now
+ *   pairs_out [4][4] u64   cells per (was, now); sums to n_cells
+ *   first_out 1            the least differing packet in (src, dst, proto,
+ *                          dport) order; live 0 and zeros if there is none
+ *   cells_a   [Ra+1] u64   differing cells terminating at rule k of a (Ra: the
+ *                          default DENY)
+ *   wit_a     [Ra+1]       the least differing packet terminating at rule k of
+ *                          a; zeros where there is none
+ *   cells_b, wit_b [Rb+1]  the same for b
+ *   rec_out, rec_cap, n_rec  the records (rec_out needs n_rec; n_rec alone
+ *                          counts them)
+ *   n_cells   HOST word, also with CLS_F_DEVICE: Ks Kd T
+ *   dims      HOST [4], also with CLS_F_DEVICE: the joint Ks, Kd, Kt, Ku
+ * first_out, wit_a and wit_b depend on the two lists' semantics alone (the
+ * least packet of a union of cells is the low corner of its lowest cell under
+ * any valid refinement); the counts and the records are defined relative to
+ * the joint classes and the rule structure, a deterministic function of the
+ * two lists.  No output depends on cover_tile, the evaluator or the
+ * scheduling.
+ * Flags: CLS_F_DEVICE -- every pointer not marked HOST is device memory
+ * (records and witnesses 16-byte, the u64 arrays 8-byte aligned) and the call
+ * only enqueues on `stream`; CLS_F_FORCE_LINEAR -- as cls_table_cover.
+ * CLS_E_INVAL, before any device work and with every output untouched: any
+ * other flag, af other than CLS_AF_V4 / CLS_AF_V16, a CLS_AF_V16 diff where
+ * either table has no 16-byte classifier (the message names the table), `out`
+ * NULL, none of the outputs given, rec_out without n_rec, rec_cap > 0 with
+ * rec_out NULL, a misaligned device pointer, Ks Kd T > 2^40 (the three factors
+ * in cls_last_error).  CLS_E_NOTFOUND: an unknown table on either side.  The
+ * call takes the engine's lock once and both tables as classify calls do and
+ * restores the caller's device; on a multi-device engine it runs on the first
+ * device. */
+typedef struct cls_tdiff_rec {      /* 32 bytes */
+    uint32_t src_lo, src_hi, dst_lo, dst_hi;  /* host-order IPv4, inclusive */
+    uint16_t port_lo, port_hi;                /* inclusive; 0 .. 65535 for proto 2 and 3 (port not examined) */
+    uint8_t proto;                            /* 0, 1, 2, or 3 standing for every value > 2 */
+    uint8_t was, now;                         /* ACLAction (CLS_ACL_*) under table a / table b; was != now */
+    uint8_t zero;
+    uint32_t rule_a, rule_b;                  /* terminating rule in a / in b (Ra / Rb: the default DENY) */
+} cls_tdiff_rec;
+
+typedef struct cls_tdiff_out {
+    uint64_t* n_diff;              /* 1 word: cells with was != now */
+    uint64_t* pairs_out;           /* [4][4]: cells per (was, now); sums to n_cells */
+    cls_cover_witness* first_out;  /* 1: the least differing packet; live 0 and zeros if none */
+    uint64_t* cells_a;             /* [Ra+1]: differing cells terminating at rule k of a */
+    cls_cover_witness* wit_a;      /* [Ra+1]: least differing packet terminating at rule k of a */
+    uint64_t* cells_b;             /* [Rb+1] */
+    cls_cover_witness* wit_b;      /* [Rb+1] */
+    cls_tdiff_rec* rec_out;        /* up to rec_cap records, ascending */
+    uint64_t rec_cap;
+    uint64_t* n_rec;               /* 1 word: the total, also above rec_cap */
+    uint64_t* n_cells;             /* HOST word, also with CLS_F_DEVICE */
+    uint32_t* dims;                /* HOST [4]: joint Ks, Kd, Kt, Ku */
+} cls_tdiff_out;
+
+int cls_table_diff(cls_engine* e, uint32_t table_a, uint32_t table_b, uint32_t af,
+                   const cls_tdiff_out* out, uint32_t flags, void* stream);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

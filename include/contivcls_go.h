@@ -532,6 +532,52 @@ static inline int clsg_table_cover_v16(cls_engine* e, uint32_t table_id, uint8_t
     return cls_table_cover(e, table_id, CLS_AF_V16, &o, flags, NULL);
 }
 
+/* cls_table_diff of two tables over the IPv4 packet space, IPv4 layout: the
+ * packets whose ACLAction differs between table_a and table_b.  Host arrays:
+ * n_diff (1), pairs (16: cells per (was, now)), first (one 16-byte
+ * cls_cover_witness), cells_a / wit_a over table_a's rules and its default
+ * DENY, cells_b / wit_b over table_b's, rec (rec_cap 32-byte cls_tdiff_rec)
+ * with n_rec (1: the total, also above rec_cap).  Each may be NULL, but not
+ * all, and rec needs n_rec; n_cells (1) and dims (4: the joint Ks, Kd, Kt, Ku)
+ * may be NULL. */
+static inline int clsg_table_diff_af(cls_engine* e, uint32_t af, uint32_t table_a, uint32_t table_b, uint64_t* n_diff,
+                                     uint64_t* pairs, void* first, uint64_t* cells_a, void* wit_a, uint64_t* cells_b,
+                                     void* wit_b, void* rec, uint64_t rec_cap, uint64_t* n_rec, uint64_t* n_cells,
+                                     uint32_t* dims, uint32_t flags) {
+    cls_tdiff_out o;
+    memset(&o, 0, sizeof o);
+    o.n_diff = n_diff;
+    o.pairs_out = pairs;
+    o.first_out = (cls_cover_witness*)first;
+    o.cells_a = cells_a;
+    o.wit_a = (cls_cover_witness*)wit_a;
+    o.cells_b = cells_b;
+    o.wit_b = (cls_cover_witness*)wit_b;
+    o.rec_out = (cls_tdiff_rec*)rec;
+    o.rec_cap = rec_cap;
+    o.n_rec = n_rec;
+    o.n_cells = n_cells;
+    o.dims = dims;
+    return cls_table_diff(e, table_a, table_b, af, &o, flags, NULL);
+}
+static inline int clsg_table_diff_v4(cls_engine* e, uint32_t table_a, uint32_t table_b, uint64_t* n_diff,
+                                     uint64_t* pairs, void* first, uint64_t* cells_a, void* wit_a, uint64_t* cells_b,
+                                     void* wit_b, void* rec, uint64_t rec_cap, uint64_t* n_rec, uint64_t* n_cells,
+                                     uint32_t* dims, uint32_t flags) {
+    return clsg_table_diff_af(e, CLS_AF_V4, table_a, table_b, n_diff, pairs, first, cells_a, wit_a, cells_b, wit_b, rec,
+                              rec_cap, n_rec, n_cells, dims, flags);
+}
+
+/* The same diff through the 16-byte classifier: the packets are the
+ * IPv4-mapped ::ffff:src / ::ffff:dst. */
+static inline int clsg_table_diff_v16(cls_engine* e, uint32_t table_a, uint32_t table_b, uint64_t* n_diff,
+                                      uint64_t* pairs, void* first, uint64_t* cells_a, void* wit_a, uint64_t* cells_b,
+                                      void* wit_b, void* rec, uint64_t rec_cap, uint64_t* n_rec, uint64_t* n_cells,
+                                      uint32_t* dims, uint32_t flags) {
+    return clsg_table_diff_af(e, CLS_AF_V16, table_a, table_b, n_diff, pairs, first, cells_a, wit_a, cells_b, wit_b,
+                              rec, rec_cap, n_rec, n_cells, dims, flags);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -18,7 +18,18 @@ B / A is reported per table, B also at every --tiles value (cover_tile).
 --kernel-trace --stats (a run of its own), average microseconds per launch of
 cover_expand4 / 16, cover_fold, cover_finish and of every other kernel the
 sweep launched (the classify kernels in slot mode and slot_rules_kernel).
-usage: python tools/cover_bench.py --af 4|16 [--kernel-stats]
+--diff: the table diff (cls_table_diff) instead -- each table against its
+edit (one live rule's action flipped, one live rule deleted), three ways in one
+process, alternated, each the best of --rounds windows of --iters back-to-back
+calls:
+B: cls_table_diff with device outputs (everything but the records' download);
+A: two cls_classify_rules(CLS_F_DEVICE) calls, one per table, over the joint
+   cells prebuilt in HBM, which leaves 2 x 5 B per cell (verdict and rule) to
+   download and compare on the host -- that is not in A's time;
+C: two cls_table_cover calls with device outputs, one per table.
+--kernel-stats then traces the B calls (tdiff_count, tdiff_emit,
+reach_diff_scan and cover's kernels).
+usage: python tools/cover_bench.py --af 4|16 [--diff] [--kernel-stats]
 """
 import argparse
 import csv
@@ -148,11 +159,94 @@ def measure(a):
     return out
 
 
+def edited(eng, rules, af):
+    """rules with the action of the live rule of most cells flipped (DENY <-> PERMIT; REFLECT -> DENY) and the next
+    live rule deleted."""
+    import copy
+    from vpp_amd import model as M
+    tb = eng.put_table("edit", rules)
+    cov = eng.table_cover(tb, af=af)
+    eng.del_table(tb)
+    ks = [k for k in range(len(rules)) if cov["live"][k] and rules[k].actions is not None]
+    ks.sort(key=lambda k: (-int(cov["cells"][k]), k))
+    out = [copy.deepcopy(r) for r in rules]
+    out[ks[0]].actions.acl_action = M.PERMIT if out[ks[0]].actions.acl_action == M.DENY else M.DENY
+    del out[ks[1]]
+    return out, ks[:2]
+
+
+def measure_diff(a):
+    import torch
+    from vpp_amd.engine import Engine
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    sync = torch.cuda.synchronize
+    i64, i32 = torch.int64, torch.int32
+    out = []
+    for name, rules in tables():
+        other, picked = edited(eng, rules, a.af)
+        ta, tb = eng.put_table(name, rules), eng.put_table(name + " edited", other)
+        ra, rb = len(rules) + 1, len(other) + 1
+        cap = eng.table_diff(ta, tb, af=a.af, rec_cap=0)["n_rec"] + 16
+        host = eng.table_diff(ta, tb, af=a.af, rec_cap=cap)
+        shapes = ((1,), (4, 4), (1, 4), (ra,), (ra, 4), (rb,), (rb, 4), (cap, 8), (1,))
+        res = [torch.empty(sh, dtype=dt, device="cuda") for sh, dt in zip(shapes, (i64, i64, i32, i64, i32, i64, i32, i32, i64))]
+        line = {"table": name, "rules": len(rules), "flipped_deleted": picked, "joint_dims_Ks_Kd_Kt_Ku": host["dims"],
+                "cells": host["n_cells"], "n_diff": host["n_diff"], "n_rec": host["n_rec"],
+                "pairs": host["pairs"].tolist()}
+        run_b = lambda: eng.table_diff(ta, tb, af=a.af, rec_cap=cap, out=res)
+        if a.child:
+            piped(run_b, a.iters, sync)
+            out.append(line)
+            continue
+        cov = [(torch.empty(r, dtype=torch.uint8, device="cuda"), torch.empty((r, 4), dtype=i32, device="cuda"),
+                torch.empty(r, dtype=i64, device="cuda"), torch.empty(1, dtype=i32, device="cuda")) for r in (ra, rb)]
+
+        def run_c():
+            eng.table_cover(ta, af=a.af, out=cov[0])
+            eng.table_cover(tb, af=a.af, out=cov[1])
+        c, _ = cells(list(rules) + list(other), a.af)
+        d = {k: torch.from_numpy(v.view(np.int32) if v.dtype == np.uint32 else v.view(np.int16) if v.dtype == np.uint16
+                                 else v).to("cuda") for k, v in c.items()}
+        n = len(c["proto"])
+        va, vb = (torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(2))
+        ha, hb = (torch.empty(n, dtype=i32, device="cuda") for _ in range(2))
+
+        def run_a():
+            eng.classify_rules(ta, d["src"], d["dst"], d["dport"], d["proto"], va, ha)
+            eng.classify_rules(tb, d["src"], d["dst"], d["dport"], d["proto"], vb, hb)
+        best = {"B": 1e9, "A": 1e9, "C": 1e9}
+        for _ in range(a.rounds):                       # alternated
+            for key, fn in (("B", run_b), ("A", run_a), ("C", run_c)):
+                best[key] = min(best[key], piped(fn, a.iters, sync))
+        line.update({k + "_ms": round(v, 4) for k, v in best.items()})
+        line["A_left_to_download_MB"] = round(2 * 5 * n / 1e6, 1)
+        t0 = time.perf_counter()
+        eng.table_diff(ta, tb, af=a.af, rec_cap=cap)
+        line["B_host_form_ms"] = round((time.perf_counter() - t0) * 1e3, 4)
+        sync()
+        line["A_equals_B"] = bool(int((va != vb).sum().item()) == host["n_diff"] and n == host["n_cells"])
+        dev = run_b()
+        sync()
+        line["B_device_equals_host"] = bool(
+            int(dev["n_diff"].item()) == host["n_diff"] and int(dev["n_rec"].item()) == host["n_rec"] and
+            dev["records"].cpu().numpy()[:host["n_rec"]].tobytes() == host["records"].tobytes() and
+            dev["wit_a"].cpu().numpy().tobytes() == host["wit_a"].tobytes() and
+            dev["wit_b"].cpu().numpy().tobytes() == host["wit_b"].tobytes())
+        line["B_over_C"], line["B_over_A"] = round(best["B"] / best["C"], 3), round(best["B"] / best["A"], 3)
+        out.append(line)
+        eng.del_table(ta)
+        eng.del_table(tb)
+        del d, va, vb, ha, hb
+    eng.close()
+    return out
+
+
 def kernel_stats(a):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--iters", str(a.iters),
-               "--rounds", "1", "--tiles", str(a.stats_tile)] + [x for o in a.opt for x in ("--opt", o)]
+               "--rounds", "1", "--tiles", str(a.stats_tile)] + [x for o in a.opt for x in ("--opt", o)] + \
+              (["--diff"] if a.diff else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             return {"error": r.stderr[-400:]}
@@ -163,7 +257,7 @@ def kernel_stats(a):
         for row in csv.DictReader(open(files[0])):
             name = row["Name"]
             for key in ("cover_expand4", "cover_expand16", "cover_fold_bins", "cover_fold", "cover_finish", "slot_rules_kernel",
-                        "classify4_linear"):
+                        "classify4_linear", "tdiff_count", "tdiff_emit", "reach_diff_scan"):
                 if key in name:
                     name = key
                     break
@@ -174,7 +268,7 @@ def kernel_stats(a):
             e["total_ns"] += int(row["TotalDurationNs"])
         for e in out.values():
             e["avg_us"] = round(e["total_ns"] / max(1, e["calls"]) / 1e3, 2)
-        return {"cover_tile": a.stats_tile, "both_tables_together": out}
+        return {"cover_tile": "default" if a.diff else a.stats_tile, "both_tables_together": out}
 
 
 def main():
@@ -185,15 +279,17 @@ def main():
     ap.add_argument("--tiles", type=int, nargs="+", default=[1 << 20, 1 << 22, 1 << 24])
     ap.add_argument("--chunk", type=int, default=1 << 28, help="A: cells per prebuilt chunk")
     ap.add_argument("--kernel-stats", action="store_true")
+    ap.add_argument("--diff", action="store_true", help="the table diff (cls_table_diff) against two classify calls "
+                                                        "and two cover sweeps")
     ap.add_argument("--stats-tile", type=int, default=1 << 22)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     from vpp_amd import _abi
-    lines = measure(a)
+    lines = measure_diff(a) if a.diff else measure(a)
     if a.child:
         return
-    res = {"bench": "cover", "af": a.af, "iters": a.iters, "rounds": a.rounds, "tables": lines,
+    res = {"bench": "table_diff" if a.diff else "cover", "af": a.af, "iters": a.iters, "rounds": a.rounds, "tables": lines,
            "sources": _abi.source_hash()}
     if a.kernel_stats:
         res["kernel_stats"] = kernel_stats(a)

@@ -60,7 +60,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
            "cls_port_classes", "cls_reach_hops", "cls_reach_classes",
            "cls_reach_classes_host", "cls_reach_external", "cls_addr_classes", "cls_table_cover",
-           "cls_cover_classes"]
+           "cls_cover_classes", "cls_table_diff"]
 
 
 class ClsRule(C.Structure):
@@ -162,6 +162,19 @@ class CoverOut(C.Structure):
 # cls_cover_witness as a numpy structured dtype (16 bytes)
 COVER_WITNESS = np.dtype([("src", "<u4"), ("dst", "<u4"), ("dport", "<u2"), ("proto", "u1"), ("live", "u1"),
                           ("zero", "<u4")])
+
+class TDiffOut(C.Structure):
+    """cls_tdiff_out: the outputs of cls_table_diff, each optional."""
+    _fields_ = [("n_diff", C.c_void_p), ("pairs_out", C.c_void_p), ("first_out", C.c_void_p),
+                ("cells_a", C.c_void_p), ("wit_a", C.c_void_p), ("cells_b", C.c_void_p), ("wit_b", C.c_void_p),
+                ("rec_out", C.c_void_p), ("rec_cap", C.c_uint64), ("n_rec", C.c_void_p), ("n_cells", C.c_void_p),
+                ("dims", C.c_void_p)]
+
+
+# cls_tdiff_rec as a numpy structured dtype (32 bytes)
+TDIFF_REC = np.dtype([("src_lo", "<u4"), ("src_hi", "<u4"), ("dst_lo", "<u4"), ("dst_hi", "<u4"),
+                      ("port_lo", "<u2"), ("port_hi", "<u2"), ("proto", "u1"), ("was", "u1"), ("now", "u1"),
+                      ("zero", "u1"), ("rule_a", "<u4"), ("rule_b", "<u4")])
 
 # cls_reach_classes: quot[p][A][A] of a one-member class
 CLASS_NONE = 255
@@ -311,6 +324,7 @@ def bind(path: str, strict: bool = True):
         "cls_addr_classes": (C.c_int, [vp, u32, vp, u32, C.POINTER(u32)]),
         "cls_table_cover": (C.c_int, [vp, u32, u32, C.POINTER(CoverOut), u32, vp]),
         "cls_cover_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
+        "cls_table_diff": (C.c_int, [vp, u32, u32, u32, C.POINTER(TDiffOut), u32, vp]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -274,6 +274,15 @@ struct cls_engine {
     // call downloads (witnesses, live bytes, n_dead)
     DevBuf v_tab, v_src, v_dst, v_dport, v_proto, v_rule, v_min, v_cnt, v_wit, v_live, v_dead;
     std::vector<uint8_t> cover_up;
+    // cls_table_diff (tdiff.cpp), under the same rule, beside the v_* buffers it
+    // shares (the class tables, a tile's packet arrays, table a's rules, least
+    // cells, counts and witnesses): a tile's verdict bytes under a and b, b's
+    // rules, the two masked rule arrays, b's least cells, counts and
+    // witnesses, the run heads per chunk and each chunk's first record index,
+    // the u64 words of the call (16 pair bins, n_diff, the record total, the
+    // least differing cell), the first witness and the records of a host call
+    DevBuf v_was, v_now, v_rule_b, v_mask_a, v_mask_b, v_min_b, v_cnt_b, v_wit_b, v_dcount, v_dbase, v_dacc,
+        v_first, v_rec;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

@@ -569,6 +569,39 @@ hipError_t launch_cover_fold(unsigned long long c0, uint32_t n, const uint32_t* 
 hipError_t launch_cover_finish(const CoverTile& t, const unsigned long long* minc, uint32_t n_out, uint8_t* live_out,
                                uint4* witness, uint32_t* n_dead, hipStream_t s);
 
+// ---- the table diff (k_tdiff.hip; contivcls.h cls_table_diff) --------------
+// One tile of the diff: t is a CoverTile over the JOINT classes of the two
+// tables whose c0 is a multiple of T and whose n is a whole number of rows of T
+// cells (n + T < 2^32); Ks, Kt, Ku complete the dimensions (column j < Kt: TCP,
+// j < Kt + Ku: UDP, then the ICMP column and the one of every other protocol).
+struct TDiffTile {
+    CoverTile t;
+    uint32_t Ks, Kt, Ku;
+};
+// The tile's cells under table a (was, rule_a) and table b (now, rule_b): n
+// verdict bytes and n terminating rules each, 16-B aligned.
+struct TDiffCells {
+    const uint8_t *was, *now;
+    const uint32_t *rule_a, *rule_b;
+};
+// count: a cell differs when was != now.  pairs[4 (was & 3) + (now & 3)] += the
+// cells, *n_diff += the differing ones (either may be null), *first = min(*first,
+// the least differing global cell); mask_a[i] = rule_a[i] where cell i differs
+// and none_a where not, mask_b likewise (what launch_cover_fold reduces per
+// rule with n_out = none + 1); chunk_count[chunk] = the run heads of the chunk's
+// kReachChunk cells (or null).  A run: a maximal stretch of differing cells of
+// one row and one protocol with equal (was, now, rule_a, rule_b).  Ballots in
+// the wave, 16 LDS bins per workgroup, one global add per non-zero bin.
+hipError_t launch_tdiff_count(const TDiffTile& q, const TDiffCells& c, uint32_t none_a, uint32_t none_b,
+                              uint32_t* mask_a, uint32_t* mask_b, uint32_t* chunk_count, unsigned long long* pairs,
+                              unsigned long long* n_diff, unsigned long long* first, int n_cu, hipStream_t s);
+// emit (behind launch_reach_diff_scan of the chunk counts): the record of the
+// run whose head is the chunk's k-th at rec[2 (chunk_base[chunk] + k)], two 16-B
+// stores (cls_tdiff_rec), while that index is below cap.
+hipError_t launch_tdiff_emit(const TDiffTile& q, const TDiffCells& c, const uint32_t* chunk_count,
+                             const unsigned long long* chunk_base, uint4* rec, unsigned long long cap, int n_cu,
+                             hipStream_t s);
+
 // ---- the hop closure (k_reach_hops.hip; contivcls.h cls_reach_hops) --------
 // fold: the tile's CLS_CONN_ALLOW cells off the diagonal as bits of the
 // adjacency bitmap adj[N][W], W = (N + 63) / 64 -- bit (d & 63) of word

@@ -868,6 +868,72 @@ class Engine:
         self._check(fn(self.h, tid, int(af), C.byref(o), flags | _abi.F_DEVICE, s))
         return dict(zip(names, res), n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
 
+    def table_diff(self, ta, tb, af: int = 4, mode: str = "auto", rec_cap: int = 1 << 20, out=None, stream=None):
+        """The table diff (cls_table_diff): the packets of the whole IPv4
+        packet space (``af`` 16: the same packets as ::ffff:a in the 16-byte
+        layout) whose ACLAction differs between table ``ta`` and table ``tb``,
+        over the joint classes of the two rule lists -- cover_classes and
+        port_classes of a's rules followed by b's.  Returns a dict: equal
+        (n_diff == 0), n_diff, pairs uint64 [4, 4] (cells per (was, now); sums
+        to n_cells), first (_abi.COVER_WITNESS: the least differing packet,
+        live 0 if none), cells_a uint64 [Ra+1] and wit_a [Ra+1] (differing
+        cells terminating at rule k of a and the least such packet; index Ra:
+        the default DENY), cells_b, wit_b [Rb+1], records (_abi.TDIFF_REC, one
+        per maximal run of differing cells of one row and protocol with equal
+        (was, now, rule_a, rule_b), ascending; the first min(rec_cap, n_rec)),
+        n_rec (all of them), n_cells and dims (the joint Ks, Kd, Kt, Ku).
+        mode "linear": the linear kernel evaluates.
+        out None: the host form -- numpy results, the counts ints.
+        out a sequence (n_diff, pairs, first, cells_a, wit_a, cells_b, wit_b,
+        records, n_rec) of contiguous torch GPU tensors (None allocates one):
+        the device form -- n_diff int64 [1], pairs int64 [4, 4], first int32
+        [1, 4] and wit_a / wit_b int32 [R+1, 4] rows of (src, dst, dport |
+        proto << 16 | live << 24, 0), cells_a / cells_b int64 [R+1], records
+        int32 [rec_cap, 8], n_rec int64 [1]; the call only enqueues on
+        ``stream`` (default: the engine's) and ``equal`` is None.  n_cells and
+        dims are host values either way."""
+        flags = {"auto": 0, "linear": _abi.F_FORCE_LINEAR}[mode]
+        ids = [t.id if isinstance(t, Table) else int(t) for t in (ta, tb)]
+        ra, rb = [(t.n_rules if isinstance(t, Table) else self._table_rules(i)) + 1 for t, i in zip((ta, tb), ids)]
+        rec_cap = int(rec_cap)
+        n_cells, dims = np.zeros(1, np.uint64), np.zeros(4, np.uint32)
+        fn = _abi.lib().cls_table_diff
+        names = ("n_diff", "pairs", "first", "cells_a", "wit_a", "cells_b", "wit_b", "records", "n_rec")
+        if out is None:
+            n_rec, cap = np.zeros(1, np.uint64), rec_cap
+            res = [np.zeros(1, np.uint64), np.zeros((4, 4), np.uint64), np.zeros(1, _abi.COVER_WITNESS),
+                   np.zeros(ra, np.uint64), np.zeros(ra, _abi.COVER_WITNESS), np.zeros(rb, np.uint64),
+                   np.zeros(rb, _abi.COVER_WITNESS), np.zeros(cap, _abi.TDIFF_REC), n_rec]
+            o = _abi.TDiffOut(*[_ptr(a) for a in res[:7]], _ptr(res[7]) if cap else None, cap, _ptr(n_rec),
+                              _ptr(n_cells), _ptr(dims))
+            self._check(fn(self.h, ids[0], ids[1], int(af), C.byref(o), flags, None))
+            r = dict(zip(names, res), n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
+            r["n_diff"], r["n_rec"], r["first"] = int(res[0][0]), int(n_rec[0]), res[2][0]
+            r["records"] = res[7][:min(cap, r["n_rec"])]
+            r["equal"] = r["n_diff"] == 0
+            return r
+        import torch
+        res = list(out)
+        if len(res) != len(names):
+            raise ClsError("table diff: out is (%s)" % ", ".join(names))
+        shapes = ((1,), (4, 4), (1, 4), (ra,), (ra, 4), (rb,), (rb, 4), (rec_cap, 8), (1,))
+        i64, i32 = (torch.int64, 8), (torch.int32, 4)
+        kinds = (i64, i64, i32, i64, i32, i64, i32, i32, i64)
+        for i, (sh, (dt, sz)) in enumerate(zip(shapes, kinds)):
+            if res[i] is None:
+                res[i] = torch.empty(sh, dtype=dt, device="cuda")
+            elif not (_is_torch(res[i]) and res[i].is_cuda and res[i].is_contiguous() and
+                      res[i].element_size() == sz and tuple(res[i].shape) == sh):
+                raise ClsError("table diff: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                               "elements" % (i, sh, sz))
+        s = None
+        if stream is not None:
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.TDiffOut(*[_ptr(a) for a in res[:7]], _ptr(res[7]) if rec_cap else None, rec_cap, _ptr(res[8]),
+                          _ptr(n_cells), _ptr(dims))
+        self._check(fn(self.h, ids[0], ids[1], int(af), C.byref(o), flags | _abi.F_DEVICE, s))
+        return dict(zip(names, res), equal=None, n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
+
     def _table_rules(self, tid: int) -> int:
         inf = _abi.TableInfo()
         self._check(_abi.lib().cls_table_get_info(self.h, tid, C.byref(inf)))
@@ -1654,6 +1720,52 @@ class ACLEngine:
                for k, w in enumerate(r["witness"][:n]) if w["live"]}
         return {"dead": [k for k in range(n) if not r["live"][k]], "witness": wit,
                 "default_reachable": bool(r["live"][n])}
+
+    def acl_diff(self, acl_name: str, other, af: int = 4):
+        """Whether an installed ACL and ``other`` -- another installed ACL's
+        name, or a rule list such as a candidate replacement -- give every
+        IPv4 packet the same ACLAction, and where they do not
+        (Engine.table_diff; the reference has no such call).  A rule list is
+        put as a temporary table and deleted again, also on error.  Returns a
+        dict: ``equal``; ``n_diff`` and ``n_cells``, cells of the joint class
+        product; ``pairs``, the 4 x 4 cells per (was, now) as lists;
+        ``records``, the differing packets as (src_lo, src_hi, dst_lo,
+        dst_hi) dotted quads, protocol (3 standing for every value above 2),
+        port_lo, port_hi, was, now, rule_a, rule_b, ascending; ``rules_a``
+        and ``rules_b``, rule index (the rule count: the default DENY) ->
+        (differing cells, (src, dst, protocol, dport) of the least differing
+        packet terminating there) for the rules responsible on either side.
+        As acl_coverage, the diff covers the IPv4 packet space only.  Raises
+        ClsError for an unknown name."""
+        tid = self.engine.acl_table(acl_name)
+        if acl_name not in self.by_name or tid < 0:
+            raise ClsError("acl diff: no ACL %r" % (acl_name,))
+        tmp = None
+        if isinstance(other, str):
+            tb = self.engine.acl_table(other)
+            if other not in self.by_name or tb < 0:
+                raise ClsError("acl diff: no ACL %r" % (other,))
+        else:
+            tmp = self.engine.put_table("acl_diff candidate", list(other))
+            tb = tmp
+        try:
+            r = self.engine.table_diff(tid, tb, af=af, rec_cap=0)
+            r = self.engine.table_diff(tid, tb, af=af, rec_cap=r["n_rec"])
+        finally:
+            if tmp is not None:
+                self.engine.del_table(tmp)
+
+        def ip(a):
+            return "%d.%d.%d.%d" % (a >> 24, a >> 16 & 255, a >> 8 & 255, a & 255)
+
+        def side(cells, wit):
+            return {k: (int(cells[k]), (ip(int(w["src"])), ip(int(w["dst"])), int(w["proto"]), int(w["dport"])))
+                    for k, w in enumerate(wit) if w["live"]}
+        recs = [((ip(int(c["src_lo"])), ip(int(c["src_hi"])), ip(int(c["dst_lo"])), ip(int(c["dst_hi"]))),
+                 int(c["proto"]), int(c["port_lo"]), int(c["port_hi"]), int(c["was"]), int(c["now"]),
+                 int(c["rule_a"]), int(c["rule_b"])) for c in r["records"]]
+        return {"equal": r["equal"], "n_diff": r["n_diff"], "n_cells": r["n_cells"], "pairs": r["pairs"].tolist(),
+                "records": recs, "rules_a": side(r["cells_a"], r["wit_a"]), "rules_b": side(r["cells_b"], r["wit_b"])}
 
     def connection_matrix_diff(self, pods, probes, base, count: bool = False):
         """connection_matrix against a baseline: (matrix, changes), matrix
