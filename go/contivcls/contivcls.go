@@ -1584,6 +1584,82 @@ func (en *Engine) TableCover(aclName string) (*Coverage, error) {
 	return out, nil
 }
 
+// NeededBy is why TableNeed calls a rule needed: the least packet whose
+// ACLAction changes once the rule is deleted, the action it then gets (After)
+// and the rule that then takes it (Fall; the rule count: the default DENY).
+type NeededBy struct {
+	Packet Witness
+	After  uint8
+	Fall   int
+}
+
+// Need is TableNeed's answer for one installed ACL: Dead, the rules no IPv4
+// packet terminates at; Redundant, the live rules whose packets all get the
+// same ACLAction from the rest of the list once the rule alone is gone; Free,
+// the dead and redundant rules that can be deleted together without changing
+// a verdict (redundant rules are not jointly removable in general); Needed,
+// rule index -> why; DefaultReachable; Cells, the cells the engine swept.
+type Need struct {
+	Dead, Redundant, Free []int
+	Needed                map[int]NeededBy
+	DefaultReachable      bool
+	Cells                 uint64
+}
+
+// TableNeed answers "which rules does this ACL actually need?" in one engine
+// call (cls_table_need) with the rules skip treated as deleted.  The sweep
+// covers the IPv4 packet space: a rule with an IPv6 network is reported dead.
+// The reference has no counterpart.
+func (en *Engine) TableNeed(aclName string, skip []int) (*Need, error) {
+	en.Lock()
+	defer en.Unlock()
+	var strs cstrs
+	defer strs.free()
+	var id C.uint32_t
+	if rc := C.cls_acl_table(en.e, strs.add(aclName), &id); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	var info C.cls_table_info
+	if rc := C.cls_table_get_info(en.e, id, &info); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	r := int(info.n_rules)
+	mask := make([]uint64, (r+63)/64+1)
+	for _, k := range skip {
+		if k < 0 || k >= r {
+			return nil, fmt.Errorf("contivcls: TableNeed: skip names rule %d of %d", k, r)
+		}
+		mask[k>>6] |= 1 << uint(k&63)
+	}
+	need := make([]uint8, r+1)
+	free := make([]uint8, r+1)
+	first := make([]uint64, r+1)
+	rec := make([]uint32, 4*(r+1)) // 16-byte records: src, dst, dport | proto << 16 | after << 24, fall
+	var cells C.uint64_t
+	// every slice goes to the shim as its own pointer (pointer-free Go
+	// memory); the shim builds the struct on the C stack
+	if rc := C.clsg_table_need(en.e, id, (*C.uint64_t)(&mask[0]), (*C.uint8_t)(&need[0]), (*C.uint8_t)(&free[0]),
+		(*C.uint64_t)(&first[0]), nil, unsafe.Pointer(&rec[0]), nil, &cells, nil, 0); rc != C.CLS_OK {
+		return nil, en.lastErr()
+	}
+	out := &Need{Needed: make(map[int]NeededBy), DefaultReachable: first[r] != 0, Cells: uint64(cells)}
+	for k := 0; k < r; k++ {
+		switch need[k] {
+		case C.CLS_NEED_DEAD:
+			out.Dead = append(out.Dead, k)
+		case C.CLS_NEED_REDUNDANT:
+			out.Redundant = append(out.Redundant, k)
+		case C.CLS_NEED_NEEDED:
+			out.Needed[k] = NeededBy{Packet: Witness{Src: rec[4*k], Dst: rec[4*k+1], Protocol: uint8(rec[4*k+2] >> 16),
+				DstPort: uint16(rec[4*k+2])}, After: uint8(rec[4*k+2]>>24) & 3, Fall: int(rec[4*k+3])}
+		}
+		if free[k] != 0 {
+			out.Free = append(out.Free, k)
+		}
+	}
+	return out, nil
+}
+
 // DiffRecord is one run of packets whose ACLAction differs between two ACLs:
 // source and destination address ranges (host order, inclusive), Protocol 0
 // TCP, 1 UDP, 2 ICMP and 3 standing for every other value, the destination

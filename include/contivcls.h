@@ -62,7 +62,10 @@ extern "C" {
  *    for each of the others: cls_cover_witness, cls_cover_out),
  *    cls_cover_classes and the cover_tile option; cls_table_diff (the packets
  *    whose verdict differs between two tables, as records over the joint
- *    classes, and the rules responsible: cls_tdiff_rec, cls_tdiff_out). */
+ *    classes, and the rules responsible: cls_tdiff_rec, cls_tdiff_out);
+ *    cls_table_need (the rules a table can lose without changing a verdict:
+ *    cls_need_witness, cls_need_out, CLS_NEED_*), its device-free twin
+ *    cls_table_need_host and the need_bitmap_mb and need_cols_lds options. */
 #define CLS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -214,7 +217,7 @@ int cls_abi_version(void);
  * conn_jobs, conn_plan=32j|16j|32s|16s, conn_flush_atomic, batch_layout,
  * reach_tile -- cls_reach_matrix's connections per tile, 256 .. 2^30, rounded
  * up to a multiple of 1024 --, cover_tile -- cls_table_cover's cells per tile,
- * 1024 .. 2^30, rounded up likewise --, hops_rows, classes_key_bits, debug_modes, debug_conn, debug_floor) for
+ * 1024 .. 2^30, rounded up likewise --, need_bitmap_mb, need_cols_lds, hops_rows, classes_key_bits, debug_modes, debug_conn, debug_floor) for
  * later calls; every one keeps verdicts and counters exact.  The library never reads the environment:
  * an engine runs its defaults unless told otherwise here.  CLS_E_INVAL for
  * an unknown key or a malformed value. */
@@ -957,6 +960,98 @@ typedef struct cls_tdiff_out {
 
 int cls_table_diff(cls_engine* e, uint32_t table_a, uint32_t table_b, uint32_t af,
                    const cls_tdiff_out* out, uint32_t flags, void* stream);
+
+/* ---- rule necessity sweep: rules a table can lose without changing a verdict
+ * "Which rules does this list actually need?"  A rule can be live (packets
+ * terminate at it) and still be removable: every packet it takes gets the same
+ * ACLAction from the rest of the list once the rule is gone.  The space, the
+ * classes, the cell numbering c = (s Kd + d) T + j and the columns are
+ * cls_table_cover's (Table classes of the one list): every IPv4 packet (src,
+ * dst, proto, dport).  Native IPv6 packets are out of scope: a rule with an
+ * IPv6 network takes no IPv4 packet and is reported dead by this sweep.
+ * For a table of R rules and an optional set `skip` of rules treated as
+ * deleted (a HOST bitmask of (R + 63) / 64 u64 words, bit r & 63 of word r >>
+ * 6, copied before the call returns; NULL: none):
+ *   first(c)   the lowest rule outside skip that terminates cell c; R: the
+ *              default DENY
+ *   second(c)  the next such rule above first(c); R if none
+ *   act(k, c)  rule k's ACLAction for the cell's protocol (a FAILURE at the
+ *              rule is an action of its own); CLS_ACL_DENY for k = R
+ *   cell c CHANGES UNDER r iff first(c) == r and act(second(c), c) != act(r, c)
+ * In the reduced form of the rules (evalACL, aclengine_mock.go:473-668) "rule k
+ * terminates packet x" is (source class of x in k's source set) AND
+ * (destination class in k's destination set) AND (column in k's column set), so
+ * the set of ALL rules that would take a cell is the AND of three bit rows, one
+ * bit per rule: its lowest set bit is first, the next one second.  This
+ * evaluator is independent of the compiled classifiers, which encode first
+ * matches only.
+ * Per rule r (need_out): CLS_NEED_SKIPPED -- r is in skip; CLS_NEED_DEAD -- no
+ * cell has first == r; CLS_NEED_REDUNDANT -- some cell has, and none changes
+ * under r; CLS_NEED_NEEDED -- some cell changes under r.  need[r] != NEEDED
+ * holds exactly when the list without r alone (and without skip) gives every
+ * IPv4 packet the same ACLAction.  Redundant rules are not jointly removable
+ * (two equal PERMITs: each is redundant given the other), so free_out[r] = 1
+ * iff r is DEAD, or r is REDUNDANT and every cell with first == r has a second
+ * that is NEEDED or the default: all free rules can be deleted together
+ * without changing a verdict, and unless no rule is dead or redundant at least
+ * one rule is free.
+ * Outputs (cls_need_out), each optional; one of the first six must be given:
+ *   need_out    [R] u8     CLS_NEED_*
+ *   free_out    [R] u8
+ *   first_out   [R+1] u64  the cells with first == k under skip; sums to Ks Kd
+ *                          T; with no skip cls_table_cover's cells_out
+ *   changed_out [R] u64    the cells that change under r (relative to the
+ *                          classes, a deterministic function of the list)
+ *   witness_out [R]        for a NEEDED rule the LEAST packet in (src, dst,
+ *                          proto, dport) order that changes under r, `after`
+ *                          the ACLAction it gets without r with bit 7 set as
+ *                          the valid mark, `fall` the rule that then takes it
+ *                          (R: the default); all zero for every other rule.
+ *                          Canonical as cls_table_cover's witness: the low
+ *                          corner of the lowest changing cell
+ *   counts      [4] u32    rules per CLS_NEED_* value
+ *   n_cells     HOST word, also with CLS_F_DEVICE: Ks Kd T
+ *   dims        HOST [4], also with CLS_F_DEVICE: Ks, Kd, Kt, Ku
+ * No output depends on cover_tile (the sweep goes in tiles of max(1,
+ * cover_tile / T) whole (s, d) pairs), on the need_cols_lds option (the column
+ * rows in LDS or read from global memory) or on the scheduling.
+ * Flags: CLS_F_DEVICE only -- the first six outputs are device memory
+ * (witness_out 16-byte, first_out and changed_out 8-byte, counts 4-byte
+ * aligned) and the call only enqueues on `stream`.  CLS_E_INVAL, before any
+ * device work and with every output untouched: `out` NULL or none of the six
+ * outputs, any other flag, a misaligned device pointer, Ks Kd T > 2^40, bit
+ * rows -- (Ks + Kd + T + 1) rows of (R + 63) / 64 u64 words -- above the
+ * need_bitmap_mb option's MiB (default 1024; the numbers in cls_last_error).
+ * CLS_E_NOTFOUND: an unknown table.  Lock, table lifetime and the caller's
+ * device as cls_table_cover. */
+enum { CLS_NEED_SKIPPED = 0, CLS_NEED_DEAD = 1, CLS_NEED_REDUNDANT = 2, CLS_NEED_NEEDED = 3 };
+
+typedef struct cls_need_witness {    /* 16 bytes */
+    uint32_t src, dst;               /* host-order IPv4 */
+    uint16_t dport;
+    uint8_t proto;                   /* 0, 1, 2, or 3 standing for every value > 2 */
+    uint8_t after;                   /* 0x80 | the ACLAction without the rule; 0: the rule is not NEEDED */
+    uint32_t fall;                   /* the rule that takes the packet then; R: the default DENY */
+} cls_need_witness;
+
+typedef struct cls_need_out {
+    uint8_t* need_out;               /* [R] */
+    uint8_t* free_out;               /* [R] */
+    uint64_t* first_out;             /* [R+1] */
+    uint64_t* changed_out;           /* [R] */
+    cls_need_witness* witness_out;   /* [R] */
+    uint32_t* counts;                /* [4] */
+    uint64_t* n_cells;               /* HOST word, also with CLS_F_DEVICE */
+    uint32_t* dims;                  /* HOST [4]: Ks, Kd, Kt, Ku */
+} cls_need_out;
+
+int cls_table_need(cls_engine* e, uint32_t table_id, const uint64_t* skip, const cls_need_out* out, uint32_t flags,
+                   void* stream);
+/* The same definition with no device: plain C++ over the same bit rows (the
+ * CPU baseline; every pointer host memory).  CLS_E_INVAL: `out` NULL or none
+ * of the six outputs, rules NULL with n_rules > 0, a rule with nil Matches,
+ * Ks Kd T > 2^40. */
+int cls_table_need_host(const cls_rule* rules, uint32_t n_rules, const uint64_t* skip, const cls_need_out* out);
 
 /* ---- synthetic traffic (BASELINE.md / SURVEY 8(d) generator) -----------
  * Generates packets i in [first, first+n) of the counter-based splitmix64

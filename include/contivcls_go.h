@@ -578,6 +578,30 @@ static inline int clsg_table_diff_v16(cls_engine* e, uint32_t table_a, uint32_t 
                               rec, rec_cap, n_rec, n_cells, dims, flags);
 }
 
+/* cls_table_need of one table over the IPv4 packet space: the rules the list
+ * can lose without changing a verdict.  skip: (r + 63) / 64 u64 words, bit k
+ * set for a rule treated as deleted, or NULL.  Host arrays over the table's r
+ * rules: need and free (r u8), first (r + 1 u64, index r the default DENY),
+ * changed (r u64), witness (r records of 16 bytes: src and dst as u32, dport
+ * as u16, proto and after as u8, fall as u32), counts (4 u32: rules per
+ * CLS_NEED_* value) may each be NULL, but not all; n_cells (1) and dims (4:
+ * Ks, Kd, Kt, Ku) may be NULL. */
+static inline int clsg_table_need(cls_engine* e, uint32_t table_id, const uint64_t* skip, uint8_t* need, uint8_t* free_out,
+                                  uint64_t* first, uint64_t* changed, void* witness, uint32_t* counts,
+                                  uint64_t* n_cells, uint32_t* dims, uint32_t flags) {
+    cls_need_out o;
+    memset(&o, 0, sizeof o);
+    o.need_out = need;
+    o.free_out = free_out;
+    o.first_out = first;
+    o.changed_out = changed;
+    o.witness_out = (cls_need_witness*)witness;
+    o.counts = counts;
+    o.n_cells = n_cells;
+    o.dims = dims;
+    return cls_table_need(e, table_id, skip, &o, flags, NULL);
+}
+
 /* The pinned host array of a batch field (CLS_BATCH_MIRROR), NULL if none:
  * C memory, so Go may keep it as a slice (Go 1.9: (*[1 << 32]T)(p)[:n:n]). */
 static inline void* clsg_batch_mirror(cls_batch* b, uint32_t field) {

@@ -29,7 +29,19 @@ A: two cls_classify_rules(CLS_F_DEVICE) calls, one per table, over the joint
 C: two cls_table_cover calls with device outputs, one per table.
 --kernel-stats then traces the B calls (tdiff_count, tdiff_emit,
 reach_diff_scan and cover's kernels).
-usage: python tools/cover_bench.py --af 4|16 [--diff] [--kernel-stats]
+--need: the rule necessity sweep (cls_table_need) instead, in one process,
+alternated, each the best of --rounds windows of --iters back-to-back calls:
+B: cls_table_need with every device output, and B_no_free without free_out
+   (no second pass over the cells);
+A: cls_table_cover with device outputs on the same table -- the floor of one
+   pass over the cells;
+C: what a user does without the call, per rule: put the list without r and
+   cls_table_diff against it; timed for 16 rules and EXTRAPOLATED to R.
+Once each: cls_table_need_host, the counts per need value, the rounds and the
+result size of the minimizing round loop (checked with cls_table_diff), and the
+same sweep with need_cols_lds=0.  --kernel-stats then traces the B calls
+(need_bits, need_cells, need_mark, need_free, need_finish and cover's folds).
+usage: python tools/cover_bench.py --af 4|16 [--diff | --need] [--kernel-stats]
 """
 import argparse
 import csv
@@ -241,12 +253,92 @@ def measure_diff(a):
     return out
 
 
+def measure_need(a):
+    import torch
+    from vpp_amd.engine import Engine, minimize_rounds
+    eng = Engine(options=dict(o.split("=", 1) for o in a.opt))
+    sync = torch.cuda.synchronize
+    i64, i32, u8 = torch.int64, torch.int32, torch.uint8
+    out = []
+    for name, rules in tables():
+        tb = eng.put_table(name, rules)
+        r = len(rules)
+        res = [torch.empty(r, dtype=u8, device="cuda"), torch.empty(r, dtype=u8, device="cuda"),
+               torch.empty(r + 1, dtype=i64, device="cuda"), torch.empty(r, dtype=i64, device="cuda"),
+               torch.empty((r, 4), dtype=i32, device="cuda"), torch.empty(4, dtype=i32, device="cuda")]
+        run_b = lambda: eng.table_need(tb, out=res)
+        run_b1 = lambda: eng.table_need(tb, out=[res[0], False] + res[2:])
+        if a.child:
+            piped(run_b, a.iters, sync)
+            out.append({"table": name})
+            eng.del_table(tb)
+            continue
+        host = eng.table_need(tb)
+        line = {"table": name, "rules": r, "dims_Ks_Kd_Kt_Ku": host["dims"], "cells": host["n_cells"],
+                "W_words": max(1, (r + 63) // 64), "counts_skipped_dead_redundant_needed": host["counts"].tolist(),
+                "free": int(host["free"].sum()), "default_reachable": bool(host["first"][r])}
+        cov = (torch.empty(r + 1, dtype=u8, device="cuda"), torch.empty((r + 1, 4), dtype=i32, device="cuda"),
+               torch.empty(r + 1, dtype=i64, device="cuda"), torch.empty(1, dtype=i32, device="cuda"))
+        run_a = lambda: eng.table_cover(tb, af=a.af, out=cov)
+        best = {"B": 1e9, "B_no_free": 1e9, "A": 1e9}
+        for _ in range(a.rounds):                       # alternated
+            for key, fn in (("B", run_b), ("B_no_free", run_b1), ("A", run_a)):
+                best[key] = min(best[key], piped(fn, a.iters, sync))
+        line.update({k + "_ms": round(v, 4) for k, v in best.items()})
+        line["B_over_A"] = round(best["B"] / best["A"], 3)
+        eng.set_option("need_cols_lds", 0)
+        line["B_cols_global_ms"] = round(min(piped(run_b, a.iters, sync) for _ in range(a.rounds)), 4)
+        glob_form = eng.table_need(tb)
+        eng.set_option("need_cols_lds", None)
+        line["cols_global_equals_lds"] = all(glob_form[k].tobytes() == host[k].tobytes() for k in
+                                             ("need", "free", "first", "changed", "witness", "counts"))
+        t0 = time.perf_counter()
+        eng.table_need(tb)
+        line["B_host_form_ms"] = round((time.perf_counter() - t0) * 1e3, 4)
+        dev = run_b()
+        sync()
+        line["B_device_equals_host"] = all(dev[k].cpu().numpy().tobytes() == host[k].tobytes() for k in
+                                           ("need", "free", "first", "changed", "witness", "counts"))
+        cvr = eng.table_cover(tb, af=a.af)
+        line["first_equals_cover_cells"] = bool(np.array_equal(host["first"], cvr["cells"]))
+        # C: put + diff per rule, 16 rules spread over the list
+        picks = sorted(set(int(x) for x in np.linspace(0, r - 1, 16)))
+        t0 = time.perf_counter()
+        agree = True
+        for k in picks:
+            t2 = eng.put_table(name + " without", rules[:k] + rules[k + 1:])
+            d = eng.table_diff(tb, t2, af=a.af, rec_cap=0)
+            eng.del_table(t2)
+            agree = agree and d["equal"] == (host["need"][k] != 3)
+        per = (time.perf_counter() - t0) / len(picks) * 1e3
+        line["C_put_and_diff_ms_per_rule"] = round(per, 3)
+        line["C_extrapolated_to_R_ms"] = round(per * r, 1)
+        line["C_agrees_with_need_on_the_16"] = bool(agree)
+        t0 = time.perf_counter()
+        cpu = Engine.table_need_host(rules)
+        line["need_host_cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+        line["need_host_equals_device"] = all(cpu[k].tobytes() == host[k].tobytes() for k in
+                                              ("need", "free", "first", "changed", "witness", "counts"))
+        t0 = time.perf_counter()
+        kept, rounds = minimize_rounds(lambda skip: eng.table_need(tb, skip=skip), r)
+        line["minimize_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+        line["minimize_rounds"], line["minimized_rules"] = len(rounds), len(kept)
+        line["removed_per_round"] = [len(x) for x in rounds]
+        t2 = eng.put_table(name + " minimized", [rules[k] for k in kept])
+        line["minimized_diffs_equal"] = bool(eng.table_diff(tb, t2, af=a.af, rec_cap=0)["equal"])
+        eng.del_table(t2)
+        out.append(line)
+        eng.del_table(tb)
+    eng.close()
+    return out
+
+
 def kernel_stats(a):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--child", "--af", str(a.af), "--iters", str(a.iters),
                "--rounds", "1", "--tiles", str(a.stats_tile)] + [x for o in a.opt for x in ("--opt", o)] + \
-              (["--diff"] if a.diff else [])
+              (["--diff"] if a.diff else []) + (["--need"] if a.need else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             return {"error": r.stderr[-400:]}
@@ -257,7 +349,8 @@ def kernel_stats(a):
         for row in csv.DictReader(open(files[0])):
             name = row["Name"]
             for key in ("cover_expand4", "cover_expand16", "cover_fold_bins", "cover_fold", "cover_finish", "slot_rules_kernel",
-                        "classify4_linear", "tdiff_count", "tdiff_emit", "reach_diff_scan"):
+                        "classify4_linear", "tdiff_count", "tdiff_emit", "reach_diff_scan", "need_bits", "need_cells",
+                        "need_mark", "need_free", "need_finish"):
                 if key in name:
                     name = key
                     break
@@ -268,7 +361,7 @@ def kernel_stats(a):
             e["total_ns"] += int(row["TotalDurationNs"])
         for e in out.values():
             e["avg_us"] = round(e["total_ns"] / max(1, e["calls"]) / 1e3, 2)
-        return {"cover_tile": "default" if a.diff else a.stats_tile, "both_tables_together": out}
+        return {"cover_tile": "default" if a.diff or a.need else a.stats_tile, "both_tables_together": out}
 
 
 def main():
@@ -281,15 +374,17 @@ def main():
     ap.add_argument("--kernel-stats", action="store_true")
     ap.add_argument("--diff", action="store_true", help="the table diff (cls_table_diff) against two classify calls "
                                                         "and two cover sweeps")
+    ap.add_argument("--need", action="store_true", help="the rule necessity sweep (cls_table_need) against one cover "
+                                                        "sweep and against put + diff per rule")
     ap.add_argument("--stats-tile", type=int, default=1 << 22)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE")
     a = ap.parse_args()
     from vpp_amd import _abi
-    lines = measure_diff(a) if a.diff else measure(a)
+    lines = measure_need(a) if a.need else measure_diff(a) if a.diff else measure(a)
     if a.child:
         return
-    res = {"bench": "table_diff" if a.diff else "cover", "af": a.af, "iters": a.iters, "rounds": a.rounds, "tables": lines,
+    res = {"bench": "table_need" if a.need else "table_diff" if a.diff else "cover", "af": a.af, "iters": a.iters, "rounds": a.rounds, "tables": lines,
            "sources": _abi.source_hash()}
     if a.kernel_stats:
         res["kernel_stats"] = kernel_stats(a)

@@ -60,7 +60,7 @@ SYMBOLS = ["cls_abi_version", "cls_engine_create", "cls_engine_destroy", "cls_la
            "cls_comm_init", "cls_comm_info", "cls_reach_matrix", "cls_reach_diff", "cls_reach_ports",
            "cls_port_classes", "cls_reach_hops", "cls_reach_classes",
            "cls_reach_classes_host", "cls_reach_external", "cls_addr_classes", "cls_table_cover",
-           "cls_cover_classes", "cls_table_diff"]
+           "cls_cover_classes", "cls_table_diff", "cls_table_need", "cls_table_need_host"]
 
 
 class ClsRule(C.Structure):
@@ -175,6 +175,19 @@ class TDiffOut(C.Structure):
 TDIFF_REC = np.dtype([("src_lo", "<u4"), ("src_hi", "<u4"), ("dst_lo", "<u4"), ("dst_hi", "<u4"),
                       ("port_lo", "<u2"), ("port_hi", "<u2"), ("proto", "u1"), ("was", "u1"), ("now", "u1"),
                       ("zero", "u1"), ("rule_a", "<u4"), ("rule_b", "<u4")])
+
+class NeedOut(C.Structure):
+    """cls_need_out: the outputs of cls_table_need and cls_table_need_host, each optional."""
+    _fields_ = [("need_out", C.c_void_p), ("free_out", C.c_void_p), ("first_out", C.c_void_p),
+                ("changed_out", C.c_void_p), ("witness_out", C.c_void_p), ("counts", C.c_void_p),
+                ("n_cells", C.c_void_p), ("dims", C.c_void_p)]
+
+
+# cls_table_need's need values
+NEED_SKIPPED, NEED_DEAD, NEED_REDUNDANT, NEED_NEEDED = 0, 1, 2, 3
+# cls_need_witness as a numpy structured dtype (16 bytes); after: 0x80 | the ACLAction without the rule
+NEED_WITNESS = np.dtype([("src", "<u4"), ("dst", "<u4"), ("dport", "<u2"), ("proto", "u1"), ("after", "u1"),
+                         ("fall", "<u4")])
 
 # cls_reach_classes: quot[p][A][A] of a one-member class
 CLASS_NONE = 255
@@ -325,6 +338,8 @@ def bind(path: str, strict: bool = True):
         "cls_table_cover": (C.c_int, [vp, u32, u32, C.POINTER(CoverOut), u32, vp]),
         "cls_cover_classes": (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(u32)]),
         "cls_table_diff": (C.c_int, [vp, u32, u32, u32, C.POINTER(TDiffOut), u32, vp]),
+        "cls_table_need": (C.c_int, [vp, u32, vp, C.POINTER(NeedOut), u32, vp]),
+        "cls_table_need_host": (C.c_int, [vp, u32, vp, C.POINTER(NeedOut)]),
         "cls_acl_stats": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "cls_gen_traffic_v4": (C.c_int, [vp, C.POINTER(TrafficSpec), u64, u64, vp, vp, vp, vp,
                                          vp, vp]),

@@ -92,8 +92,10 @@ inline uint32_t v4_mask(int len) { return len ? (0xFFFFFFFFu << (32 - len)) : 0u
 
 }  // namespace
 
+bool matches_everything_rule(const SemRule& s) { return matches_everything(s); }
+
 int semantic_rules(const cls_rule* rules, uint32_t n, int fam, std::vector<SemRule>& out,
-                   std::string& err) {
+                   std::string& err, bool keep_unreachable) {
     out.clear();
     for (uint32_t k = 0; k < n; ++k) {
         const cls_rule& r = rules[k];
@@ -108,13 +110,18 @@ int semantic_rules(const cls_rule* rules, uint32_t n, int fam, std::vector<SemRu
         if ((r.flags & CLS_R_MACIP) || !(r.flags & CLS_R_IPRULE) || (r.flags & CLS_R_OTHER) ||
             !(r.flags & CLS_R_IP)) {
             out.push_back(terminator(k));
+            if (keep_unreachable) continue;
             return CLS_OK;
         }
         SemRule s;
         s.index = k;
         if (nonempty(r.src_network)) {                       // :499-510
             s.src = parse_cidr(r.src_network);
-            if (s.src.fam == 0) { out.push_back(terminator(k)); return CLS_OK; }
+            if (s.src.fam == 0) {
+                out.push_back(terminator(k));
+                if (keep_unreachable) continue;
+                return CLS_OK;
+            }
             if (fam && s.src.fam != fam) continue;           // never Contains() this family
             s.src_any = false;
         }
@@ -140,7 +147,7 @@ int semantic_rules(const cls_rule* rules, uint32_t n, int fam, std::vector<SemRu
         for (const auto& t : s.t) any_term |= t.term;
         if (!any_term) continue;
         out.push_back(s);
-        if (matches_everything(s)) return CLS_OK;            // later rules unreachable
+        if (matches_everything(s) && !keep_unreachable) return CLS_OK;   // later rules unreachable
     }
     return CLS_OK;
 }

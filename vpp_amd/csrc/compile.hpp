@@ -80,8 +80,12 @@ struct SemRule {
 // Reduce the ACL for packets of family `fam` (4: both addresses IPv4; 0: each
 // address of either family -- networks of both families kept).  Returns CLS_OK or
 // CLS_E_INVAL (a rule with nil Matches: Go would panic).
+// keep_unreachable: the rules behind one that matches every packet are reduced
+// too (cls_table_need asks what takes over once a rule is deleted).
 int semantic_rules(const cls_rule* rules, uint32_t n, int fam, std::vector<SemRule>& out,
-                   std::string& err);
+                   std::string& err, bool keep_unreachable = false);
+// The rule terminates every packet of every protocol: semantic_rules stops behind it.
+bool matches_everything_rule(const SemRule& s);
 
 // ---- linear table (device layout, 48 B per rule) ---------------------------
 struct alignas(16) LinRule4 {

@@ -345,6 +345,13 @@ static int table_compile(cls_engine* e, const char* name, const cls_rule* rules,
     if (rc != CLS_OK) return fail(e, rc, "%s", why.c_str());
     t->lin4 = linear4(sem);
     t->conn4 = conn_rules4(sem);
+    // rules cut off behind one that matches every packet: cls_table_need's list keeps them
+    if (!sem.empty() && sem.back().index + 1 < n && matches_everything_rule(sem.back())) {
+        std::vector<SemRule> all;
+        rc = semantic_rules(rules, n, 4, all, why, true);
+        if (rc != CLS_OK) return fail(e, rc, "%s", why.c_str());
+        if (all.size() != sem.size()) t->need4 = linear4(all);
+    }
     // classifier for anything but tiny tables
     t->kernel = 0;
     if (sem.size() > 8 && build_pair(sem, n, t->img, t->oimg, why)) {
@@ -412,6 +419,7 @@ std::shared_ptr<Table> table_clone_host(const Table& s) {
     for (int p = 0; p < 2; ++p) t->port_lo[p] = s.port_lo[p];
     t->addr_lo = s.addr_lo;
     for (int sd = 0; sd < 2; ++sd) t->cover_lo[sd] = s.cover_lo[sd];
+    t->need4 = s.need4;
     t->conn_bm = s.conn_bm;
     t->conn_bm_built = s.conn_bm_built;
     t->conn_epoch = s.conn_epoch;

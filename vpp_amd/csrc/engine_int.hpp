@@ -157,6 +157,13 @@ struct Table {
     // cls_table_cover: the class starts of the source (0) and the destination
     // (1) networks alone (cover_side_starts: sorted, unique, the first is 0)
     std::vector<uint32_t> cover_lo[2];
+    // cls_table_need: the reduced IPv4 rules with those behind a rule that
+    // matches every packet kept (semantic_rules keep_unreachable) -- what takes
+    // over once that rule is deleted.  Empty where lin4 is already that list;
+    // d_need4: its device copy, uploaded by the first cls_table_need
+    std::vector<LinRule4> need4;
+    DevBuf d_need4;
+    bool need4_up = false;
     // the bitmap form of conn4 (conn_bitmap4), built on the first connection
     // batch that wants it; empty when its tables exceed kConnBmMaxWords
     std::vector<uint32_t> conn_bm;
@@ -283,6 +290,15 @@ struct cls_engine {
     // least differing cell), the first witness and the records of a host call
     DevBuf v_was, v_now, v_rule_b, v_mask_a, v_mask_b, v_min_b, v_cnt_b, v_wit_b, v_dcount, v_dbase, v_dacc,
         v_first, v_rec;
+    // cls_table_need (need.cpp), under the same rule, beside v_tab (the class
+    // tables, the result bytes), v_rule and v_mask_a (a tile's first matches
+    // and its masked array): the bit rows S | D | C | kept, the need and free
+    // bytes, the witnesses and the four counts of a host call, the per-rule
+    // cell counts (first, changing, chained: three rows of R + 2 u64) and least
+    // cells (changing; one row the folds of the other two arrays write and
+    // nobody reads).  need_up: the host copy of the upload
+    DevBuf nd_bits, nd_need, nd_free, nd_wit, nd_counts, nd_cnt, nd_min;
+    std::vector<uint8_t> need_up;
     // A device connection batch is stream-ordered (connect_locked): the stream
     // of the last one while it may still run, waited for before its scratch,
     // plan or tables change (conn_quiesce); a batch on another stream waits

@@ -602,6 +602,60 @@ hipError_t launch_tdiff_emit(const TDiffTile& q, const TDiffCells& c, const uint
                              const unsigned long long* chunk_base, uint4* rec, unsigned long long cap, int n_cu,
                              hipStream_t s);
 
+// ---- the rule necessity sweep (k_need.hip; contivcls.h cls_table_need) -----
+// The sweep's tables.  slo / dlo / col: cover's class tables.  bits: the bit
+// rows, one bit per rule (bit r & 63 of word r >> 6), W = max(1, (R + 63) / 64)
+// u64 words per row, each section's start rounded up to a whole 16 B: S[Ks]
+// at word 0, D[Kd] at word wD, C[T] at wC, the kept row (~skip, tail bits
+// clear) at wK.  res: one byte per rule, two ACLAction bits per protocol
+// (TCP, UDP, ICMP, every other value), [R] zero for the default DENY.
+struct NeedTab {
+    uint32_t Ks, Kd, T, W, R;
+    uint32_t wD, wC, wK;
+    const uint32_t *slo, *dlo, *col;
+    unsigned long long* bits;
+    const uint8_t* res;
+};
+// The reduced rule's tests of a class start and of a column: what a bit of an
+// S, D or C row says (host and device: cls_table_need_host builds the same rows).
+__host__ __device__ inline bool need_src_hit(const LinRule4& l, uint32_t a) { return (a & l.src_mask) == l.src_addr; }
+__host__ __device__ inline bool need_dst_hit(const LinRule4& l, uint32_t a) { return (a & l.dst_mask) == l.dst_addr; }
+__host__ __device__ inline bool need_col_hit(const LinRule4& l, uint32_t col) {
+    const uint32_t p = col >> 16 & 3u, w = l.port[p];
+    return (l.meta >> (8u * p) & 0x80u) && (col & 0xFFFFu) - (w & 0xFFFFu) <= w >> 16;
+}
+__host__ __device__ inline uint8_t need_res_byte(uint32_t meta) {
+    return uint8_t((meta & 3u) | (meta >> 8 & 3u) << 2 | (meta >> 16 & 3u) << 4 | (meta >> 24 & 3u) << 6);
+}
+// The S, D and C rows from the n_lin reduced rules (ascending LinRule4::index
+// below R; a rule absent from the list sets no bit): one thread per output
+// word, 64 rule tests each.  The kept row is the caller's.
+hipError_t launch_need_bits(const NeedTab& q, const LinRule4* lin, uint32_t n_lin, hipStream_t s);
+// One tile of whole (s, d) pairs: `pairs` of them from pair0 = s Kd + d on,
+// tile cell i = (pair - pair0) T + j (pairs T < 2^32).  One wave per pair; the
+// column rows in LDS when cols_lds (the caller checked that T W 8 bytes fit
+// need_cols_lds_max()).  need == null, the first pass: first[i] = first(c),
+// mark[i] = first(c) where the cell changes under it, R + 1 where not.
+// need != null (the R need bytes), the second pass: mark[i] = first(c) where
+// second(c) is a rule that is not CLS_NEED_NEEDED, R + 1 elsewhere; first
+// unused.  Both arrays are what launch_cover_fold reduces with n_out = R + 2.
+hipError_t launch_need_cells(const NeedTab& q, unsigned long long pair0, uint32_t pairs, const uint8_t* need,
+                             uint32_t* first, uint32_t* mark, bool cols_lds, int n_cu, hipStream_t s);
+uint32_t need_cols_lds_max();
+// Once per call over the R rules: need[r] from the kept row and the two count
+// rows (cells with first == r, cells changing under r); counts[need[r]] += 1
+// (cleared before; or null); changed[r] = cnt_chg[r] (or null).
+hipError_t launch_need_mark(const NeedTab& q, const unsigned long long* cnt_first, const unsigned long long* cnt_chg,
+                            uint8_t* need, uint32_t* counts, unsigned long long* changed, hipStream_t s);
+// free[r] = DEAD, or REDUNDANT with no chained cell.
+hipError_t launch_need_free(uint32_t R, const uint8_t* need, const unsigned long long* cnt_chain, uint8_t* free_out,
+                            hipStream_t s);
+// Rule r's least changing cell min_chg[r] -> its witness {src, dst, dport |
+// proto << 16 | (0x80 | after) << 24, fall}, second recomputed for that one
+// cell; zeros for a rule that is not CLS_NEED_NEEDED.
+hipError_t launch_need_finish(const NeedTab& q, const unsigned long long* min_chg, const uint8_t* need, uint4* witness,
+                              hipStream_t s);
+
 // ---- the hop closure (k_reach_hops.hip; contivcls.h cls_reach_hops) --------
 // fold: the tile's CLS_CONN_ALLOW cells off the diagonal as bits of the
 // adjacency bitmap adj[N][W], W = (N + 63) / 64 -- bit (d & 63) of word

@@ -82,7 +82,16 @@ bool opts_set(Opts& o, const char* key, const char* value, std::string& why) {
     OPT("conn_flush_atomic", conn_flush_atomic, b)
     OPT("debug_conn", debug_conn, b)
     OPT("batch_layout", batch_layout, i)
+    OPT("need_cols_lds", need_cols_lds, b)
 #undef OPT
+    if (k == "need_bitmap_mb") {
+        if (!reset && (x < 0 || x > (1ll << 20))) {
+            why = "option need_bitmap_mb: 0 .. 2^20 MiB";
+            return false;
+        }
+        o.need_bitmap_mb = reset ? d.need_bitmap_mb : uint32_t(x);
+        return true;
+    }
     if (k == "pair_qcap") {
         o.pair_qcap = reset ? d.pair_qcap : uint32_t(x);
         o.pair_qcap_set = !reset;

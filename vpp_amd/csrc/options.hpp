@@ -61,7 +61,9 @@ struct Opts {
                                      // measured best of 1 / 4 / 16 Mi, profiles/reach_ab_af{4,16}.txt)
     uint32_t cover_tile = 16u << 20; // cls_table_cover: cells per tile (1024 .. 2^30, rounded up to a multiple of 1024; 16 Mi
                                      // measured best of 1 / 4 / 16 Mi on config 3, profiles/cover_ab_af{4,16}.txt)
-    uint32_t hops_rows = 0;     // cls_reach_hops: source rows per workgroup of the search, 4, 8 or 16 (0: 4, the
+    uint32_t need_bitmap_mb = 1024;  // cls_table_need: refuse bit rows above this many MiB (a safety cap, not a tuned number)
+    bool need_cols_lds = true;       // cls_table_need: the column rows in LDS where they fit (0: always from global memory)
+    uint32_t hops_rows = 0;    // cls_reach_hops: source rows per workgroup of the search, 4, 8 or 16 (0: 4, the
                                 // best of the three measured, profiles/reach_hops_ab_af{4,16}.txt; halved while
                                 // the rows do not fit 64 KiB of LDS)
     uint32_t classes_key_bits = 64;  // cls_reach_classes, diagnostics: the low bits of the row and column sums kept

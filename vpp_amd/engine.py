@@ -934,6 +934,101 @@ class Engine:
         self._check(fn(self.h, ids[0], ids[1], int(af), C.byref(o), flags | _abi.F_DEVICE, s))
         return dict(zip(names, res), equal=None, n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
 
+    @staticmethod
+    def _skip_mask(skip, r: int) -> np.ndarray:
+        """``skip`` -- None, an iterable of rule indices, or the uint64
+        bitmask itself -- as the (r + 63) // 64 words cls_table_need takes."""
+        words = max(1, (r + 63) // 64)
+        if isinstance(skip, np.ndarray) and skip.dtype == np.uint64:
+            if len(skip) < (r + 63) // 64:
+                raise ClsError("table need: skip has %d words, %d rules need %d" % (len(skip), r, (r + 63) // 64))
+            return np.ascontiguousarray(skip)
+        m = np.zeros(words, np.uint64)
+        for k in (() if skip is None else skip):
+            k = int(k)
+            if not 0 <= k < r:
+                raise ClsError("table need: skip names rule %d of %d" % (k, r))
+            m[k >> 6] |= np.uint64(1 << (k & 63))
+        return m
+
+    @staticmethod
+    def _need_result(res, n_cells, dims):
+        names = ("need", "free", "first", "changed", "witness", "counts")
+        return dict(zip(names, res), n_cells=int(n_cells[0]), dims=tuple(int(x) for x in dims))
+
+    @staticmethod
+    def table_need_host(rules, skip=None):
+        """cls_table_need_host: table_need's host form computed without a
+        device, in plain C++ over the same bit rows (the CPU baseline)."""
+        cr = rules if isinstance(rules, _abi.CRules) else _abi.CRules(rules)
+        r = cr.n
+        m = Engine._skip_mask(skip, r)
+        n_cells, dims = np.zeros(1, np.uint64), np.zeros(4, np.uint32)
+        res = [np.zeros(r, np.uint8), np.zeros(r, np.uint8), np.zeros(r + 1, np.uint64), np.zeros(r, np.uint64),
+               np.zeros(r, _abi.NEED_WITNESS), np.zeros(4, np.uint32)]
+        o = _abi.NeedOut(*[_ptr(a) for a in res], _ptr(n_cells), _ptr(dims))
+        rc = _abi.lib().cls_table_need_host(cr.ptr(), cr.n, _ptr(m), C.byref(o))
+        if rc != 0:
+            raise ClsError("cls_table_need_host: rc=%d" % rc)
+        return Engine._need_result(res, n_cells, dims)
+
+    def table_need(self, table, skip=None, out=None, stream=None):
+        """The rule necessity sweep (cls_table_need) of one table over the
+        whole IPv4 packet space: which rules the list can lose without
+        changing any packet's ACLAction.  ``skip``: rules treated as deleted
+        (indices, or the uint64 bitmask).  Returns a dict: need uint8 [R]
+        (_abi.NEED_SKIPPED / NEED_DEAD / NEED_REDUNDANT / NEED_NEEDED), free
+        uint8 [R] (1: deletable together with every other free rule), first
+        uint64 [R+1] (cells whose first match is the rule; index R: the
+        default DENY; sums to n_cells), changed uint64 [R] (cells whose action
+        changes without the rule), witness [R] (_abi.NEED_WITNESS: for a
+        NEEDED rule the least packet that changes, after = 0x80 | the action
+        it gets without the rule, fall = the rule that takes it then; zeros
+        otherwise), counts uint32 [4] (rules per need value), n_cells and dims
+        (Ks, Kd, Kt, Ku).  Native IPv6 packets are out of scope: a rule with
+        an IPv6 network is reported dead.
+        out None: the host form -- numpy results.
+        out a sequence (need, free, first, changed, witness, counts) of
+        contiguous torch GPU tensors (None allocates one; False leaves that
+        output out, which spares the second pass when it is free): the device
+        form -- need and free uint8 [R], first int64 [R+1], changed int64 [R],
+        witness int32 [R, 4] rows of (src, dst, dport | proto << 16 | after <<
+        24, fall), counts int32 [4]; the call only enqueues on ``stream``
+        (default: the engine's).  n_cells and dims are host values either way."""
+        tid = table.id if isinstance(table, Table) else int(table)
+        r = table.n_rules if isinstance(table, Table) else self._table_rules(tid)
+        m = self._skip_mask(skip, r)
+        n_cells, dims = np.zeros(1, np.uint64), np.zeros(4, np.uint32)
+        fn = _abi.lib().cls_table_need
+        if out is None:
+            res = [np.zeros(r, np.uint8), np.zeros(r, np.uint8), np.zeros(r + 1, np.uint64), np.zeros(r, np.uint64),
+                   np.zeros(r, _abi.NEED_WITNESS), np.zeros(4, np.uint32)]
+            o = _abi.NeedOut(*[_ptr(a) for a in res], _ptr(n_cells), _ptr(dims))
+            self._check(fn(self.h, tid, _ptr(m), C.byref(o), 0, None))
+            return self._need_result(res, n_cells, dims)
+        import torch
+        res = list(out)
+        if len(res) != 6:
+            raise ClsError("table need: out is (need, free, first, changed, witness, counts)")
+        shapes = ((r,), (r,), (r + 1,), (r,), (r, 4), (4,))
+        kinds = ((torch.uint8, 1), (torch.uint8, 1), (torch.int64, 8), (torch.int64, 8), (torch.int32, 4),
+                 (torch.int32, 4))
+        for i, (sh, (dt, sz)) in enumerate(zip(shapes, kinds)):
+            if res[i] is False:
+                res[i] = None
+            elif res[i] is None:
+                res[i] = torch.empty(sh, dtype=dt, device="cuda")
+            elif not (_is_torch(res[i]) and res[i].is_cuda and res[i].is_contiguous() and
+                      res[i].element_size() == sz and tuple(res[i].shape) == sh):
+                raise ClsError("table need: out[%d] must be a contiguous GPU tensor of shape %s, %d-byte "
+                               "elements" % (i, sh, sz))
+        s = None
+        if stream is not None:
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        o = _abi.NeedOut(*[_ptr(a) for a in res], _ptr(n_cells), _ptr(dims))
+        self._check(fn(self.h, tid, _ptr(m), C.byref(o), _abi.F_DEVICE, s))
+        return self._need_result(res, n_cells, dims)
+
     def _table_rules(self, tid: int) -> int:
         inf = _abi.TableInfo()
         self._check(_abi.lib().cls_table_get_info(self.h, tid, C.byref(inf)))
@@ -1357,6 +1452,50 @@ def _ip4(ip: Optional[bytes]) -> Optional[int]:
     return int.from_bytes(x, "big")
 
 
+def v6_rules(rules):
+    """The indices of the rules with an IPv6 (family-16) source or
+    destination network: an IPv4 sweep sees them as dead, and they exist for
+    packets it does not cover."""
+    out = []
+    for k, r in enumerate(rules):
+        ipr = r.matches.ip_rule if r.matches is not None else None
+        ip = ipr.ip if ipr is not None else None
+        if ip is None:
+            continue
+        for s in (ip.source_network, ip.destination_network):
+            net = gonet.parse_cidr(s)[1] if s else None
+            nn = net._network_number_and_mask()[0] if net is not None else None
+            if nn is not None and len(nn) == 16:
+                out.append(k)
+                break
+    return out
+
+
+def minimize_rounds(sweep, n_rules: int, keep=(), max_rounds: int = 64):
+    """The round loop of ACLEngine.acl_minimize over any form of the sweep:
+    ``sweep(skip)`` returns table_need's dict for the set ``skip`` of deleted
+    rules.  Each round deletes every free rule outside ``keep`` -- all free
+    rules can go together without changing a verdict, and while a rule is dead
+    or redundant at least one is free (the highest redundant rule can only
+    fall to rules above it, none of them redundant) --; it stops when no rule
+    outside ``keep`` is dead or redundant, or after ``max_rounds``.  Returns
+    (kept rule indices, removed indices per round)."""
+    keep = set(int(k) for k in keep)
+    skip, rounds = set(), []
+    for _ in range(max_rounds):
+        r = sweep(sorted(skip))
+        loose = [k for k in range(n_rules) if k not in keep and k not in skip and
+                 r["need"][k] in (_abi.NEED_DEAD, _abi.NEED_REDUNDANT)]
+        if not loose:
+            break
+        gone = [k for k in loose if r["free"][k]]
+        if not gone:              # only where keep pins the rules the loose ones fall to
+            break
+        rounds.append(gone)
+        skip.update(gone)
+    return [k for k in range(n_rules) if k not in skip], rounds
+
+
 class ACLEngine:
     """MockACLEngine drop-in over the GPU engine (aclengine_mock.go:94-471)."""
 
@@ -1766,6 +1905,67 @@ class ACLEngine:
                  int(c["rule_a"]), int(c["rule_b"])) for c in r["records"]]
         return {"equal": r["equal"], "n_diff": r["n_diff"], "n_cells": r["n_cells"], "pairs": r["pairs"].tolist(),
                 "records": recs, "rules_a": side(r["cells_a"], r["wit_a"]), "rules_b": side(r["cells_b"], r["wit_b"])}
+
+    def acl_needed(self, acl_name: str, keep=()):
+        """Which rules an installed ACL actually needs (Engine.table_need over
+        the ACL's compiled table; the reference has no such call).  Returns a
+        dict: ``dead``, the rules no packet terminates at; ``redundant``, the
+        live rules whose packets all get the same ACLAction from the rest of
+        the list once the rule alone is gone; ``free``, the dead and
+        redundant rules that can be deleted TOGETHER without changing a
+        verdict (redundant rules are not jointly removable in general: of two
+        equal PERMITs each is redundant given the other); ``needed``, rule
+        index -> (src string, dst string, protocol, dport, after, fall): the
+        least packet whose action changes without the rule, the action it
+        then gets and the rule that then takes it (the rule count: the default
+        DENY); ``default_reachable``.  ``keep``: rules never reported free.
+        The sweep covers the IPv4 packet space only: a rule with an IPv6
+        network is reported dead.  Raises ClsError for an unknown name."""
+        tid = self.engine.acl_table(acl_name)
+        if acl_name not in self.by_name or tid < 0:
+            raise ClsError("acl needed: no ACL %r" % (acl_name,))
+        r = self.engine.table_need(tid)
+        n = len(r["need"])
+        keep = set(int(k) for k in keep)
+
+        def ip(a):
+            return "%d.%d.%d.%d" % (a >> 24, a >> 16 & 255, a >> 8 & 255, a & 255)
+        needed = {k: (ip(int(w["src"])), ip(int(w["dst"])), int(w["proto"]), int(w["dport"]), int(w["after"]) & 3,
+                      int(w["fall"])) for k, w in enumerate(r["witness"]) if w["after"] & 0x80}
+        return {"dead": [k for k in range(n) if r["need"][k] == _abi.NEED_DEAD],
+                "redundant": [k for k in range(n) if r["need"][k] == _abi.NEED_REDUNDANT],
+                "free": [k for k in range(n) if r["free"][k] and k not in keep], "needed": needed,
+                "default_reachable": bool(r["first"][n])}
+
+    def acl_minimize(self, acl_name: str, keep=(), keep_v6: bool = True, max_rounds: int = 64):
+        """A smaller rule list with the same ACLAction for every IPv4 packet:
+        (kept rule indices, removed indices per round).  Computes only --
+        nothing is installed.  Rounds of Engine.table_need with a growing
+        ``skip`` (minimize_rounds): each round removes every free rule outside
+        ``keep``, until no rule outside ``keep`` is dead or redundant or
+        ``max_rounds`` is reached (a rule that can only fall to a redundant
+        rule pinned by ``keep`` stays).  The result is then checked with
+        Engine.table_diff, the original against the reduced list, and ClsError
+        is raised if they are not equal.  ``keep_v6`` pins every rule with an
+        IPv6 (family-16) source or destination network: the IPv4 sweep sees
+        those as dead, and they exist for packets the sweep does not cover."""
+        tid = self.engine.acl_table(acl_name)
+        acl = self.by_name.get(acl_name)
+        if acl is None or tid < 0:
+            raise ClsError("acl minimize: no ACL %r" % (acl_name,))
+        rules = list(acl.rules)
+        pinned = set(int(k) for k in keep) | (set(v6_rules(rules)) if keep_v6 else set())
+        kept, rounds = minimize_rounds(lambda skip: self.engine.table_need(tid, skip=skip), len(rules), pinned,
+                                       max_rounds)
+        if rounds:
+            tmp = self.engine.put_table("acl_minimize result", [rules[k] for k in kept])
+            try:
+                d = self.engine.table_diff(tid, tmp, rec_cap=0)
+            finally:
+                self.engine.del_table(tmp)
+            if not d["equal"]:
+                raise ClsError("acl minimize: the reduced list of %r differs on %d cells" % (acl_name, d["n_diff"]))
+        return kept, rounds
 
     def connection_matrix_diff(self, pods, probes, base, count: bool = False):
         """connection_matrix against a baseline: (matrix, changes), matrix
